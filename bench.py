@@ -3,7 +3,10 @@
 configs[1]: B=32 clips x 32 mel frames -> 8192 samples, 80-mel, 22.05 kHz, inference), one process per
 GPU.  Prints ONE JSON line on rank 0 (contract in the task description).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16|fp16] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16|fp16] [--no-cpu-baseline] [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes the waveform batch of the last timed step (rank 0; float32, [B, 1, 256 * frames]) to DIR/wave.npy.
+Weights and inputs are seeded, so the same arguments give the same inputs on every run and two builds can be compared on it.
 
 `--gpus N` (N > 1) without a torchrun environment starts `python -m torch.distributed.run` with N ranks as a CHILD
 process before anything touches the GPU and relays its output; under torchrun (WORLD_SIZE set) each rank runs in place.
@@ -256,7 +259,10 @@ def main():
     ap.add_argument("--train-dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--train-eager", action="store_true", help="issue the training step eagerly instead of replaying its HIP graph")
     ap.add_argument("--no-train-alt", action="store_true", help="skip the fp32 / fp16 activation legs of the training metric")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the waveform of the last timed step (rank 0) to DIR/wave.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -342,9 +348,14 @@ def main():
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        wave = step()
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "wave.npy"), wave.detach().float().cpu().numpy())
+    del wave
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

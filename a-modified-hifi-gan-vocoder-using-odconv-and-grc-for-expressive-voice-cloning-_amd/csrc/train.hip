@@ -34,6 +34,25 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(uint8_t* __restrict__
   }
 }
 
+// Counter-offset form of the same mask: counter (blk lo, blk hi, ctr lo, ctr hi) - ctr = 0 gives dropout_mask_kernel's bits.  With
+// `state` set, {key, ctr_base} (int64) come from device memory and ctr = ctr_base + `ctr` (the mask's slot in the step): a captured
+// HIP graph then draws new masks whenever the host advances ctr_base between replays.
+__global__ __launch_bounds__(256) void dropout_mask_ctr_kernel(uint8_t* __restrict__ mask, long n, uint32_t thresh16,
+                                                               const long long* __restrict__ state, uint64_t key, uint64_t ctr) {
+  if (state) { key = (uint64_t)state[0]; ctr += (uint64_t)state[1]; }
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32), c2 = (uint32_t)ctr, c3 = (uint32_t)(ctr >> 32);
+  const long nblk = (n + 7) / 8;
+  for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblk; blk += (long)gridDim.x * blockDim.x) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), c2, c3, k0, k1, r);
+    uint8_t m[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m[e] = ((r[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= thresh16 ? 1 : 0;   // keep iff u >= p
+    if (blk * 8 + 8 <= n) *reinterpret_cast<uint2*>(mask + blk * 8) = *reinterpret_cast<const uint2*>(m);
+    else for (int e = 0; blk * 8 + e < n; ++e) mask[blk * 8 + e] = m[e];
+  }
+}
+
 // ------------------------------------------------------------------------------------------- GRC fold backward
 // forward (norm_elem.hip grc_fold_kernel): comb[o'][c][j] = [c in grp(o')] Wc[o'][c_loc][j] + [j==mid] s (A B)[c][o']
 //   w_eff[o][c][j] = sum_o' Wp[o][o'] comb[o'][c][j];  b_eff[o] = sum_o' Wp[o][o'] bc[o'] + bp[o]
@@ -191,6 +210,26 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
                                                         float wd, const int* __restrict__ step, float gscale) {
+  const float t = (float)(*step);
+  const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float gr = g[i] * gscale;
+    float pi = p[i] * (1.f - lr * wd);
+    const float mi = b1 * m[i] + (1.f - b1) * gr;
+    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    p[i] = pi;
+  }
+}
+
+// the same with every per-step input in device memory: {lr, beta1, beta2, eps, weight_decay} (fp32) and the step count (int32) - the
+// host refreshes them before each replay of a captured step, so schedules, lr changes and restored counts reach the graph
+__global__ __launch_bounds__(256) void adamw_hp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, long n, const float* __restrict__ hp,
+                                                       const int* __restrict__ step, float gscale) {
+  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4];
   const float t = (float)(*step);
   const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -377,6 +416,29 @@ extern "C" int mv_dropout_mask(uint8_t* mask, long n, float p, long seed_, void*
   return MV_OK;
 }
 
+static inline unsigned dropout_grid(long n) {
+  const long nblk = (n + 7) / 8;
+  return (unsigned)((nblk + 255) / 256 > 4096 ? 4096 : (nblk + 255) / 256);
+}
+
+extern "C" int mv_dropout_mask_ctr(uint8_t* mask, long n, float p, long key, long ctr, void* stream) {
+  MV_CHECK_ARG(mask && n > 0 && p >= 0.f && p < 1.f && ((uintptr_t)mask & 7) == 0);
+  const uint32_t thresh = (uint32_t)(p * 65536.f + 0.5f);
+  hipLaunchKernelGGL(dropout_mask_ctr_kernel, dim3(dropout_grid(n)), dim3(256), 0, (hipStream_t)stream, mask, n, thresh,
+                     (const long long*)nullptr, (uint64_t)key, (uint64_t)ctr);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_dropout_mask_dev(uint8_t* mask, long n, float p, const long* state_dev, long slot, void* stream) {
+  MV_CHECK_ARG(mask && state_dev && n > 0 && p >= 0.f && p < 1.f && ((uintptr_t)mask & 7) == 0 && ((uintptr_t)state_dev & 7) == 0);
+  const uint32_t thresh = (uint32_t)(p * 65536.f + 0.5f);
+  hipLaunchKernelGGL(dropout_mask_ctr_kernel, dim3(dropout_grid(n)), dim3(256), 0, (hipStream_t)stream, mask, n, thresh,
+                     (const long long*)state_dev, (uint64_t)0, (uint64_t)slot);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
 extern "C" int mv_grc_fold_bwd(const float* g_weff, const float* g_beff, const void* conv_w, const void* conv_b,
                                const void* lora_A, const void* lora_B, const void* lora_scaling, const void* proj_w,
                                float* g_conv_w, float* g_conv_b, float* g_A, float* g_B, float* g_s, float* g_proj_w,
@@ -443,6 +505,15 @@ extern "C" int mv_adamw_flat_dev(float* p, const float* g, float* m, float* v, l
   MV_CHECK_ARG(p && g && m && v && n > 0 && step_dev);
   hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
                      beta2, eps, weight_decay, step_dev, grad_scale);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_adamw_flat_hp(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
+                                float grad_scale, void* stream) {
+  MV_CHECK_ARG(p && g && m && v && n > 0 && hparams_dev && step_dev);
+  hipLaunchKernelGGL(adamw_hp_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hparams_dev,
+                     step_dev, grad_scale);
   MV_LAUNCH_CHECK();
   return MV_OK;
 }

@@ -98,11 +98,17 @@ class VocoderTrainer:
     size is > 1) reduces each optimizer's gradient buckets UNDER its backward (parallel.OverlappedGradSync); a
     `parallel.GradSynchronizer` instance reduces the flat buffer after the backward instead; `grad_sync=False` never reduces.
     `train_step` returns host floats like the reference (:229-233); `return_tensors=True` keeps device tensors and skips the
-    device synchronisation a `.item()` costs."""
+    device synchronisation a `.item()` costs.
+
+    `dropout_rng="counter"` (the default with `use_graph`) draws the MRF dropout masks from a counter-based stream
+    (functional.DropoutRNG, key from torch's CPU generator at construction): a captured step then draws fresh masks at every replay,
+    the same ones the eager step would.  `"torch"` (the default otherwise) draws each mask's key from torch's CPU generator as
+    before - under capture those keys are frozen into the graph.  `schedulers`: lr schedules (e.g. optim.WarmupCosineLR), stepped
+    after every train_step, eager or replayed.  The dropout stream and the schedules are saved in the checkpoint."""
 
     def __init__(self, vocoder: ModifiedHiFiGANVocoder, generator_optimizer=None, discriminator_optimizer=None,
                  device=None, mel_mode: str = "stft", grad_sync=None, bucket_mib: int = 8, use_graph: bool = False,
-                 graph_warmup: int = 2):
+                 graph_warmup: int = 2, dropout_rng: Optional[str] = None, schedulers=()):
         device = device or torch.device("cuda")
         self.vocoder = vocoder.to(device)
         self.device = device
@@ -124,6 +130,11 @@ class VocoderTrainer:
         self.use_graph = use_graph
         self.graph_warmup = graph_warmup
         self._graphs = {}
+        dropout_rng = dropout_rng or ("counter" if use_graph else "torch")
+        if dropout_rng not in ("torch", "counter"):
+            raise ValueError(f"VocoderTrainer: dropout_rng must be 'torch' or 'counter', got {dropout_rng!r}")
+        self.dropout_rng = Fn.DropoutRNG.from_torch() if dropout_rng == "counter" else None
+        self.schedulers = tuple(s for s in schedulers if s is not None)
 
     @staticmethod
     def default_optimizers(vocoder, lr=2e-4, betas=(0.8, 0.99), weight_decay=1e-4):
@@ -185,9 +196,24 @@ class VocoderTrainer:
             res = self._graph_step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
         else:
             res = self._step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
+        for sch in self.schedulers:
+            sch.step()
         return res if return_tensors else self.to_floats(res)       # complete_vocoder.py:229-233 returns .item() floats
 
     def _step(self, mel_spectrogram, real_audio, speaker_embedding, emotion_embedding):
+        """One step under the trainer's dropout stream; an eager step advances the stream by the masks it drew (a captured one leaves
+        that to each replay)."""
+        rng = self.dropout_rng
+        if rng is None:
+            return self._step_body(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
+        rng.slots_used = 0
+        with Fn.use_dropout_rng(rng):
+            out = self._step_body(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
+        if not torch.cuda.is_current_stream_capturing():
+            rng.advance()
+        return out
+
+    def _step_body(self, mel_spectrogram, real_audio, speaker_embedding, emotion_embedding):
         """One step in the reference's order (complete_vocoder.py:207-226); returns device tensors."""
         out = self.vocoder(mel_spectrogram, speaker_embedding, emotion_embedding)
         fake_audio = out["generated_waveform"]
@@ -240,6 +266,11 @@ class VocoderTrainer:
             torch.cuda.current_stream().wait_stream(gs)
             return out
         gopt, dopt = self.generator_optimizer, self.discriminator_optimizer
+        rng = self.dropout_rng
+        if st["graph"] is not None and not (gopt.runs_match(st["gstate"]) and dopt.runs_match(st["dstate"])):
+            # a restored optimizer state split or merged the runs of equal step count that this graph updates: recapture
+            torch.cuda.synchronize()              # (its last replay may still be running on the pool it frees)
+            st["graph"] = st["out"] = st["gstate"] = st["dstate"] = None
         if st["graph"] is None:
             st["inputs"] = [None if t is None else t.to(self.device).clone() for t in (mel, real, spk, emo)]
             self.last_losses = None               # (loss tensors keep last step's autograd graph alive)
@@ -254,10 +285,13 @@ class VocoderTrainer:
                 graph.enable_debug_mode()
             gopt.capture_begin()
             dopt.capture_begin()
+            if rng is not None:
+                rng.device_block(self.device)     # allocated before the capture: the graph keeps its address
             try:
                 with torch.cuda.graph(graph, stream=gs):
                     st["out"] = self._step(*st["inputs"])
                 st["gstate"], st["dstate"] = gopt.capture_end(), dopt.capture_end()
+                st["dropout_slots"] = rng.slots_used if rng is not None else 0
             except Exception:
                 gopt._capture = dopt._capture = None
                 self.use_graph = False            # this configuration cannot be captured: stay eager (and say so once)
@@ -272,16 +306,26 @@ class VocoderTrainer:
         # that also carries other eager training work between replays went wrong from its second replay on (MSD gradients, then NaN) -
         # with the other work on a different stream, or nothing in between, it does not (tests/test_gpu_train_graph.py interleaves
         # an eager trainer with a captured one)
+        def replay():
+            # the host's per-step state (step counts + 1, lr and the other AdamW inputs, the dropout stream's counter) -> the state
+            # blocks the graph reads, on the replay's stream: a few hundred bytes, asynchronously
+            dopt.before_replay(st["dstate"])
+            gopt.before_replay(st["gstate"])
+            if rng is not None:
+                rng.upload()
+            st["graph"].replay()
         if os.environ.get("MV_GRAPH_REPLAY_STREAM", "own") == "own":
             cur = torch.cuda.current_stream()
             gs.wait_stream(cur)
             with torch.cuda.stream(gs):
-                st["graph"].replay()
+                replay()
             cur.wait_stream(gs)
         else:
-            st["graph"].replay()
+            replay()
         dopt.after_replay(st["dstate"])
         gopt.after_replay(st["gstate"])
+        if rng is not None:
+            rng.advance(st["dropout_slots"])
         return st["out"]
 
     @staticmethod
@@ -290,13 +334,23 @@ class VocoderTrainer:
         return {k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in losses.items()}
 
     def save_checkpoint(self, path: str):
-        torch.save({"vocoder_state_dict": self.vocoder.state_dict(),
-                    # torch.optim.AdamW's layout, so the reference's own load path (complete_vocoder.py:463-468) reads the file too
-                    "generator_optimizer_state_dict": self.generator_optimizer.torch_state_dict(),
-                    "discriminator_optimizer_state_dict": self.discriminator_optimizer.torch_state_dict()}, path)
+        ck = {"vocoder_state_dict": self.vocoder.state_dict(),
+              # torch.optim.AdamW's layout, so the reference's own load path (complete_vocoder.py:463-468) reads the file too
+              "generator_optimizer_state_dict": self.generator_optimizer.torch_state_dict(),
+              "discriminator_optimizer_state_dict": self.discriminator_optimizer.torch_state_dict()}
+        # extra keys (the reference's load path ignores them): the dropout stream and the lr schedules
+        if self.dropout_rng is not None:
+            ck["dropout_rng_state"] = self.dropout_rng.state_dict()
+        if self.schedulers:
+            ck["scheduler_state_dicts"] = [s.state_dict() for s in self.schedulers]
+        torch.save(ck, path)
 
     def load_checkpoint(self, path: str):
         ck = torch.load(path, map_location=self.device, weights_only=True)
         self.vocoder.load_state_dict(ck["vocoder_state_dict"])
         self.generator_optimizer.load_state_dict(ck["generator_optimizer_state_dict"])
         self.discriminator_optimizer.load_state_dict(ck["discriminator_optimizer_state_dict"])
+        if self.dropout_rng is not None and "dropout_rng_state" in ck:
+            self.dropout_rng.load_state_dict(ck["dropout_rng_state"])
+        for sch, sd in zip(self.schedulers, ck.get("scheduler_state_dicts", ())):
+            sch.load_state_dict(sd)

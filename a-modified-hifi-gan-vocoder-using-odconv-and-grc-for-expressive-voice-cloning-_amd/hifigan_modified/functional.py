@@ -470,13 +470,84 @@ def grc_lora_block(x, blk, out=None, out_channel_offset=0):
     return _grc_generic(x if x.stride(2) == 1 else x.contiguous(), blk)
 
 
+class DropoutRNG:
+    """Counter-based dropout stream of a trainer: mask k of a step is Philox4x32-10 under `key` at counter offset ctr_base + k (its
+    `slot`; csrc/train.hip dropout_mask_ctr_kernel), and the trainer advances ctr_base by the step's `slots_used` after every eager
+    step and every replay.  A captured step keeps only the slots: key and ctr_base are read from a device state block that the
+    trainer uploads before each replay, so every replay draws fresh masks - the same ones the eager step would draw."""
+
+    def __init__(self, key, ctr_base=0):
+        self.key, self.ctr_base, self.slots_used = int(key), int(ctr_base), 0
+        self.block = None            # optim.DeviceStateBlock {key, ctr_base} (int64) read by captured launches
+
+    @classmethod
+    def from_torch(cls):
+        """Key drawn from torch's CPU generator: `torch.manual_seed` fixes the stream."""
+        return cls(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+
+    def device_block(self, device):
+        """The state block (created on first use - call this before a capture, never inside one)."""
+        if self.block is None:
+            from .optim import DeviceStateBlock
+            self.block = DeviceStateBlock(16, device)
+        return self.block
+
+    def upload(self):
+        """{key, ctr_base} -> the device block, asynchronously on the current stream (before a replay)."""
+        import numpy as np
+        self.block.upload(np.array([self.key, self.ctr_base], dtype=np.int64))
+
+    def advance(self, slots=None):
+        self.ctr_base += self.slots_used if slots is None else slots
+        self.slots_used = 0
+
+    def state_dict(self):
+        return {"key": self.key, "ctr_base": self.ctr_base}
+
+    def load_state_dict(self, sd):
+        self.key, self.ctr_base, self.slots_used = int(sd["key"]), int(sd["ctr_base"]), 0
+
+
+_dropout_rng = None      # the DropoutRNG dropout_mask() draws from (set by a trainer for the duration of its step), or None
+
+
+class use_dropout_rng:
+    """Context manager: dropout_mask() draws from `rng` inside the block (None: from torch's CPU generator)."""
+
+    def __init__(self, rng):
+        self.rng = rng
+
+    def __enter__(self):
+        global _dropout_rng
+        self.prev, _dropout_rng = _dropout_rng, self.rng
+        return self.rng
+
+    def __exit__(self, *exc):
+        global _dropout_rng
+        _dropout_rng = self.prev
+        return False
+
+
 def dropout_mask(shape, p, device):
-    """uint8 keep-mask of nn.Dropout(p) (grc_lora.py:151,162) from our own Philox4x32-10 kernel; the 64-bit key of each mask is
-    drawn from torch's CPU generator, so `torch.manual_seed` (per rank) fixes the whole dropout stream."""
+    """uint8 keep-mask of nn.Dropout(p) (grc_lora.py:151,162) from our own Philox4x32-10 kernel.  Without an active DropoutRNG the
+    64-bit key of each mask is drawn from torch's CPU generator, so `torch.manual_seed` (per rank) fixes the whole dropout stream;
+    with one, the mask takes the stream's next slot - by value when issued eagerly, through the device state block under capture."""
     from ctypes import c_void_p
     mask = torch.empty(shape, device=device, dtype=torch.uint8)
-    seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-    N.call("mv_dropout_mask", c_void_p(mask.data_ptr()), mask.numel(), float(p), seed, ops._stream())
+    rng = _dropout_rng
+    if rng is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        N.call("mv_dropout_mask", c_void_p(mask.data_ptr()), mask.numel(), float(p), seed, ops._stream())
+        return mask
+    slot = rng.slots_used
+    rng.slots_used += 1
+    if torch.cuda.is_current_stream_capturing():
+        if rng.block is None:
+            raise RuntimeError("dropout_mask: captured under a DropoutRNG without a device state block (call device_block() first)")
+        N.call("mv_dropout_mask_dev", c_void_p(mask.data_ptr()), mask.numel(), float(p), c_void_p(rng.block.dev.data_ptr()), slot,
+               ops._stream())
+    else:
+        N.call("mv_dropout_mask_ctr", c_void_p(mask.data_ptr()), mask.numel(), float(p), rng.key, rng.ctr_base + slot, ops._stream())
     return mask
 
 

@@ -8,6 +8,7 @@ SURVEY.md §5) are left out of the arena exactly like torch.optim skips ``grad i
 """
 from __future__ import annotations
 
+import math
 from ctypes import c_void_p
 
 import numpy as np
@@ -17,6 +18,35 @@ from . import _native as N
 from . import ops
 
 _DESC = np.dtype([("src", np.uint64), ("dst_off", np.int64), ("n", np.int64), ("dtype", np.int32), ("pad", np.int32)])
+
+
+class DeviceStateBlock:
+    """A few bytes of per-step state that a captured training step reads from device memory, refreshed from the host before every
+    replay: the host stays the single source of truth (step counts, lr and the other AdamW hyper-parameters, the dropout stream's
+    counter) and the graph keeps only the block's address.  The upload is an asynchronous H2D copy from a small ring of pinned
+    buffers on the current (replay) stream; a buffer is rewritten only after the event recorded behind its last copy has completed,
+    so a host that runs ahead of the device never overwrites bytes still in flight."""
+
+    RING = 4
+
+    def __init__(self, nbytes, device):
+        self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)   # allocated outside any capture: its address is what graphs keep
+        self._ring = [[torch.zeros(nbytes, dtype=torch.uint8).pin_memory(), None] for _ in range(self.RING)]
+        self._next = 0
+
+    def upload(self, values: np.ndarray):
+        raw = np.ascontiguousarray(values).view(np.uint8).reshape(-1)
+        if raw.size != self.dev.numel():
+            raise ValueError(f"DeviceStateBlock: {raw.size} bytes for a {self.dev.numel()}-byte block")
+        slot = self._ring[self._next % self.RING]
+        self._next += 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0].numpy()[:] = raw
+        self.dev.copy_(slot[0], non_blocking=True)
+        ev = slot[1] or torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev.device))
+        slot[1] = ev
 
 
 class FlatAdamW:
@@ -172,13 +202,13 @@ class FlatAdamW:
                 for k in range(i0, i1):
                     self.steps[k] = t
             else:
-                # being captured (nothing executes now): the count lives on the device and the graph itself advances it; the host's
-                # counts move in after_replay()
-                if len(cap["runs"]) >= len(cap["steps"]):
+                # being captured (nothing executes now): the run's step count and the hyper-parameters are read from the state block
+                # that before_replay() refreshes from the host; the host's counts move in after_replay()
+                r = len(cap["runs"])
+                if r >= len(cap["planned"]):
                     raise RuntimeError("FlatAdamW: the captured step does not update the arena as one run per step count")
-                st = cap["steps"][len(cap["runs"])]
-                st.add_(1)
-                OPS.fused_adamw_dev_(*args, st, float(grad_scale))
+                blk = cap["block"].dev
+                OPS.fused_adamw_hp_(*args[:4], blk.view(torch.float32)[:5], blk.view(torch.int32)[8 + r:9 + r], float(grad_scale))
                 cap["runs"].append((i0, i1))
         self.step_count = max(self.steps)
         self._has_grad = None
@@ -188,14 +218,14 @@ class FlatAdamW:
     # ---- captured training steps (VocoderTrainer / HiFiGANTrainer with use_graph): everything the step launches is recorded once
     def capture_begin(self):
         """Call right before a training step is captured into a HIP graph (torch.cuda.graph): the gathers' descriptor tables become
-        pinned and persistent, and AdamW reads its step count from device tensors that the graph itself advances."""
+        pinned and persistent, and AdamW reads its hyper-parameters and per-run step counts from a device state block (int32 words:
+        0-4 fp32 {lr, beta1, beta2, eps, weight_decay}, 8 + r the count of run r) that before_replay() refreshes."""
         dev = self.flat_p.device
         planned = self._planned_runs()
-        # one device counter per run, set OUTSIDE the capture to the count the first replay starts from
-        steps = [torch.full((1,), self.steps[i0], dtype=torch.int32, device=dev) for (i0, _) in planned]
+        block = DeviceStateBlock(4 * (8 + len(planned)), dev)
         nbytes = self._descs.nbytes
         pinned = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(4)]
-        self._capture = {"keep": [], "steps": steps, "runs": [], "planned": planned, "pinned": pinned}
+        self._capture = {"keep": [], "block": block, "runs": [], "planned": planned, "pinned": pinned}
 
     def _planned_runs(self):
         """Runs of equal step count over ALL parameters (a captured step must give every parameter of the arena a gradient)."""
@@ -215,7 +245,22 @@ class FlatAdamW:
         if cap["runs"] != cap["planned"]:
             raise RuntimeError("FlatAdamW: the captured step left parameters without a gradient: a captured step must update every "
                                "parameter of the arena")
-        return {"keep": cap["keep"], "steps": cap["steps"], "runs": cap["runs"]}
+        return {"keep": cap["keep"], "block": cap["block"], "runs": cap["runs"]}
+
+    def runs_match(self, state):
+        """True while the host's step counts still form the runs the captured step was recorded with (a restored state can split or
+        merge them: such a graph must be recaptured, not replayed)."""
+        return self._planned_runs() == state["runs"]
+
+    def before_replay(self, state):
+        """Write this step's inputs into the captured step's state block (asynchronously, on the current stream): each run's step
+        count + 1 and the current lr / betas / eps / weight_decay, exactly what the eager step would pass."""
+        if not self.runs_match(state):
+            raise RuntimeError("FlatAdamW: the step counts no longer form the captured runs: recapture the step")
+        words = np.zeros(8 + len(state["runs"]), dtype=np.int32)
+        words[:5].view(np.float32)[:] = (self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
+        words[8:] = [self.steps[i0] + 1 for (i0, _) in state["runs"]]
+        state["block"].upload(words)
 
     def after_replay(self, state):
         """Host-side bookkeeping after one replay of a captured step: step counts and cache epochs."""
@@ -302,3 +347,61 @@ class FlatAdamW:
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
+
+
+class WarmupCosineLR:
+    """Linear warmup, then cosine decay to `min_lr` (train_config.yaml:54-72: learning_rate 2e-4, warmup_steps 2000, scheduler
+    "cosine", min_lr 1e-6), host side, in the shape of torch's LRScheduler: step() / get_last_lr() / state_dict() /
+    load_state_dict().  After s completed step() calls the lr is base_lr * f(s) with m = min_lr / base_lr and
+        f(s) = (s + 1) / W                                              s < W
+        f(s) = m + (1 - m) * (1 + cos(pi * min(1, (s - W) / (S - W)))) / 2    otherwise.
+    It sets `optimizer.lr` on a FlatAdamW and every group's 'lr' on a torch.optim optimizer; a captured training step picks the
+    value up at its next replay (FlatAdamW.before_replay)."""
+
+    def __init__(self, optimizer, warmup_steps, total_steps, min_lr=0.0):
+        if warmup_steps < 0:
+            raise ValueError(f"WarmupCosineLR: warmup_steps must be >= 0, got {warmup_steps}")
+        if total_steps <= warmup_steps:
+            raise ValueError(f"WarmupCosineLR: total_steps ({total_steps}) must exceed warmup_steps ({warmup_steps})")
+        self.optimizer = optimizer
+        self.warmup_steps, self.total_steps, self.min_lr = int(warmup_steps), int(total_steps), float(min_lr)
+        groups = getattr(optimizer, "param_groups", None)
+        if groups is not None:
+            self.base_lrs = [g.setdefault("initial_lr", g["lr"]) for g in groups]
+        else:
+            self.base_lrs = [optimizer.lr]
+        self.last_epoch = 0
+        self._apply()
+
+    def factor(self, s, base_lr):
+        W, S = self.warmup_steps, self.total_steps
+        if s < W:
+            return (s + 1) / W
+        m = self.min_lr / base_lr
+        return m + (1 - m) * 0.5 * (1 + math.cos(math.pi * min(1.0, (s - W) / (S - W))))
+
+    def _apply(self):
+        lrs = [b * self.factor(self.last_epoch, b) for b in self.base_lrs]
+        groups = getattr(self.optimizer, "param_groups", None)
+        if groups is not None:
+            for g, lr in zip(groups, lrs):
+                g["lr"] = lr
+        else:
+            self.optimizer.lr = lrs[0]
+        self._last_lr = lrs
+
+    def step(self):
+        self.last_epoch += 1
+        self._apply()
+
+    def get_last_lr(self):
+        return list(self._last_lr)
+
+    def state_dict(self):
+        return {"last_epoch": self.last_epoch, "base_lrs": list(self.base_lrs), "warmup_steps": self.warmup_steps,
+                "total_steps": self.total_steps, "min_lr": self.min_lr}
+
+    def load_state_dict(self, sd):
+        self.last_epoch, self.base_lrs = int(sd["last_epoch"]), [float(b) for b in sd["base_lrs"]]
+        self.warmup_steps, self.total_steps, self.min_lr = int(sd["warmup_steps"]), int(sd["total_steps"]), float(sd["min_lr"])
+        self._apply()

@@ -18,7 +18,7 @@ Operators (schemas as registered; ``act``: 0 none, 1 LeakyReLU, 2 tanh, 3 SiLU; 
   grc_mrf_block, generator_forward                   fused inference: grc_lora.py:157-163, SURVEY.md appendix A
   avg_pool1d, mpd_fold, disc_conv_stack              discriminators.py:72-79,94,56-66,97-107
   gan_loss, mel_loss, mel_spectrogram                complete_vocoder.py:89-184, conditioned_hifigan.py:262-265; DESIGN.md section 2
-  fused_adamw_                                       conditioned_hifigan.py:219 (torch.optim.AdamW semantics)
+  fused_adamw_, fused_adamw_dev_, fused_adamw_hp_     conditioned_hifigan.py:219 (torch.optim.AdamW semantics)
 """
 from __future__ import annotations
 
@@ -221,6 +221,25 @@ def _install():
     _LIB.impl("fused_adamw_dev_", fused_adamw_dev_, "CUDA")
     _LIB.impl("fused_adamw_dev_", _refuse_cpu("fused_adamw_dev_"), "CPU")
 
+    # every per-step input in device memory (hparams: fp32 {lr, beta1, beta2, eps, weight_decay}; step: int32, already incremented):
+    # what a captured training step replays, the host refreshing both before each replay
+    _LIB.define("fused_adamw_hp_(Tensor(a!) p, Tensor g, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor hparams, Tensor step, "
+                "float grad_scale) -> ()")
+
+    def fused_adamw_hp_(p, g, m, v, hparams, step, gscale):
+        from ctypes import c_void_p
+        if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
+                any(t.dtype != torch.float32 or t.numel() != p.numel() for t in (p, g, m, v)):
+            raise RuntimeError(f"{NS}::fused_adamw_hp_: p, g, exp_avg, exp_avg_sq must be contiguous fp32 tensors of one size")
+        if hparams.dtype != torch.float32 or hparams.numel() != 5 or not hparams.is_contiguous() or not hparams.is_cuda:
+            raise RuntimeError(f"{NS}::fused_adamw_hp_: hparams must be a contiguous five-element fp32 GPU tensor")
+        if step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
+            raise RuntimeError(f"{NS}::fused_adamw_hp_: step must be a one-element int32 GPU tensor")
+        N.call("mv_adamw_flat_hp", c_void_p(p.data_ptr()), c_void_p(g.data_ptr()), c_void_p(m.data_ptr()), c_void_p(v.data_ptr()),
+               p.numel(), c_void_p(hparams.data_ptr()), c_void_p(step.data_ptr()), float(gscale), ops._stream())
+    _LIB.impl("fused_adamw_hp_", fused_adamw_hp_, "CUDA")
+    _LIB.impl("fused_adamw_hp_", _refuse_cpu("fused_adamw_hp_"), "CPU")
+
 
 def _install_fakes():
     """Shape / dtype functions (torch.library.register_fake): FakeTensor tracing (torch.compile, torch.export, opcheck) sees through
@@ -300,6 +319,10 @@ def _install_fakes():
 
     @fake("fused_adamw_dev_")
     def _(p, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale):
+        return None
+
+    @fake("fused_adamw_hp_")
+    def _(p, g, exp_avg, exp_avg_sq, hparams, step, grad_scale):
         return None
 
 

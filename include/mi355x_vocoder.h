@@ -357,9 +357,21 @@ int mv_adamw_flat(float* p, const float* g, float* m, float* v, long n, float lr
 /* the same with the step count (>= 1, already incremented) read from device memory: the form a captured HIP graph replays */
 int mv_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                       float weight_decay, const int* step_dev, float grad_scale, void* stream);
+/* the same with every per-step input in device memory (conditioned_hifigan.py:219 AdamW driven by the schedule of
+ * train_config.yaml:54-72): hparams_dev = {lr, beta1, beta2, eps, weight_decay} fp32, step_dev = the step count (>= 1, int32).
+ * Same arithmetic as mv_adamw_flat_dev: a captured training step reads what the host uploaded before the replay. */
+int mv_adamw_flat_hp(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
+                     float grad_scale, void* stream);
 /* uint8 keep-mask of nn.Dropout(p) (grc_lora.py:151,162): mask[i] = 1 with probability 1-p, Philox4x32-10 keyed by `seed`,
  * counter = element index / 8 (16 random bits per element; resolution 2^-16 on p). */
 int mv_dropout_mask(uint8_t* mask, long n, float p, long seed, void* stream);
+/* The counter-offset form (grc_lora.py:151,162 nn.Dropout in train mode, applied by a training step that is replayed as a graph):
+ * Philox4x32-10 counter (i/8 lo, i/8 hi, ctr lo, ctr hi) under key (key lo, key hi); ctr = 0 gives mv_dropout_mask's bits.
+ *   mv_dropout_mask_ctr: key and ctr by value (eager steps).
+ *   mv_dropout_mask_dev: state_dev (device, 8-byte aligned) = {key, ctr_base} int64, ctr = ctr_base + slot - a captured graph
+ *     keeps `slot` and reads the rest at replay time, so new masks follow whenever the host advances ctr_base. */
+int mv_dropout_mask_ctr(uint8_t* mask, long n, float p, long key, long ctr, void* stream);
+int mv_dropout_mask_dev(uint8_t* mask, long n, float p, const long* state_dev, long slot, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Channels-last MFMA discriminator convolutions.   replaces discriminators.py:57-65 (Conv2d 3x3 pad 1) and :98-106

@@ -377,9 +377,7 @@ using namespace mv;
 
 // internal (not part of the C ABI): used by the MRF chain's fused ending, mrf_fused.hip
 bool mvi_conv_out_affine_takes_partials(int dtype, int ks) {
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("MV_CONV_OUT_MFMA"); use_mfma = e ? atoi(e) : 1; }
-  return dtype == MV_F32 && use_mfma && ks <= 16;
+  return dtype == MV_F32 && ks <= 16;
 }
 
 int mvi_conv_out_affine(const void* f, const void* x, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
@@ -389,9 +387,7 @@ int mvi_conv_out_affine(const void* f, const void* x, const float* ab, const flo
   if (x_pair && !(dtype == MV_F32 && mvi_conv_out_affine_takes_partials(dtype, ks))) return MV_ERR_UNSUPPORTED;
   if (part8 && !mvi_conv_out_affine_takes_partials(dtype, ks)) return MV_ERR_UNSUPPORTED;
   dim3 grid(cdiv(T_, 256), B);
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("MV_CONV_OUT_MFMA"); use_mfma = e ? atoi(e) : 1; }
-  if (dtype == MV_F32 && use_mfma && ks <= 16) {
+  if (dtype == MV_F32 && ks <= 16) {
     const size_t rows16 = (size_t)((256 + ks - 1 + 15) / 16) * 16;
     const size_t lds = rows16 * (2 * 64 * 2 + 16);       // >= the z tile (16 x 288 floats)
     if (x_pair < 0 || x_pair > 4) return MV_ERR_ARG;
@@ -470,9 +466,7 @@ extern "C" int mv_conv_out_act_packed_cl(const void* x, const void* packed, floa
   const char* pk = (const char*)packed;
   if (dtype == MV_F32) return mv_conv_out_act_cl(x, (const float*)pk, bias, y, B, T_, C, ks, pad, act, dtype, stream);
   dim3 grid(cdiv(T_, 256), B);
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("MV_CONV_OUT_MFMA"); use_mfma = e ? atoi(e) : 1; }
-  if (use_mfma && ks <= 16 && (dtype == MV_BF16 || dtype == MV_F16)) {
+  if (ks <= 16 && (dtype == MV_BF16 || dtype == MV_F16)) {
     const size_t ldsm = (size_t)((256 + ks - 1 + 15) / 16) * 16 * (64 * 2 + 16);      // >= the z tile (16 x 288 floats = 18 KB)
     if (dtype == MV_BF16)
       hipLaunchKernelGGL((conv_out_mfma16_kernel<bf16, 64>), grid, dim3(256), ldsm, (hipStream_t)stream, (const bf16*)x,

@@ -17,9 +17,6 @@
 
 namespace mv {
 
-#ifdef MV_DC_TIMING
-__device__ long long* dc_dbg = nullptr;
-#endif
 struct DcP {
   int B, H, W, Cin, Cout, kh, kw, act;
   float slope;
@@ -1008,12 +1005,6 @@ __global__ __launch_bounds__(512, 2) void dconv_wgrad3_kernel(const T* __restric
   }
   __syncthreads();
   int par = 0;
-#ifdef MV_DC_TIMING
-  long long tacc[5] = {0, 0, 0, 0, 0}, tprev = clock64(), tnow;
-#define W3_TM(i) do { tnow = clock64(); tacc[i] += tnow - tprev; tprev = tnow; } while (0)
-#else
-#define W3_TM(i) do {} while (0)
-#endif
   for (int chunk = cbeg; chunk < cend; ++chunk) {
     const bool more = chunk + 1 < cend;                     // uniform across the workgroup
     // the next chunk and the x rows it adds: one row below in the same strip, or rows 0 and 1 of the next strip
@@ -1030,7 +1021,6 @@ __global__ __launch_bounds__(512, 2) void dconv_wgrad3_kernel(const T* __restric
       toff[t] = XBASE + ((hh >= 0 && hh < H) ? ((v - 1 + ih) & 7) : ZSLOT) * PBUF + iw * RS;
     }
     const char* gbase = lds + par * GBUF;
-    W3_TM(0);
     if (do_gb) {                                            // bias gradient from the staged g tile: 8 channels x 2 rows per thread
       constexpr int RPP = 512 / OPC;
 #pragma unroll
@@ -1041,7 +1031,6 @@ __global__ __launch_bounds__(512, 2) void dconv_wgrad3_kernel(const T* __restric
         for (int e = 0; e < 8; ++e) bsum[e] += ld<T>(tmp + e);
       }
     }
-    W3_TM(1);
 #pragma unroll 1
     for (int k0 = 0; k0 < WT; k0 += 32) {
       typename M::V a[MO];
@@ -1068,20 +1057,11 @@ __global__ __launch_bounds__(512, 2) void dconv_wgrad3_kernel(const T* __restric
         }
       }
     }
-    W3_TM(2);
     if (more) commit(true, par ^ 1, s0, s1);
-    W3_TM(3);
     __syncthreads();
-    W3_TM(4);
     par ^= 1;
     b = nb; wc = nwc; h = nh; v = nv;
   }
-#ifdef MV_DC_TIMING
-  if (tid == 0 && dc_dbg) {
-    const long wgid = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (wgid < 4096) { for (int i = 0; i < 5; ++i) dc_dbg[wgid * 8 + i] = tacc[i] / (cend - cbeg); dc_dbg[wgid * 8 + 5] = cend - cbeg; dc_dbg[wgid * 8 + 6] = dc_dbg[wgid * 8 + 7] = -1; }
-  }
-#endif
   if (do_gb) {                                              // row-slice sums -> one atomic per channel and workgroup
     float* red = reinterpret_cast<float*>(lds);            // [512 / OPC slices][OT] (the loop's last barrier is behind us)
 #pragma unroll
@@ -1390,21 +1370,16 @@ static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias
   if (dtype != MV_F32 && B * H <= 65535) {
     // 8-wave chunked variant: picked where it measured faster than the whole-Cin tile (tools/bench_dconv.py, B=32):
     // every wide input (Cin > 128), and narrow outputs of 3x3 layers, where the whole-Cin kernel leaves waves idle
-    static int force = -2;
-    if (force == -2) { const char* e = getenv("MV_DCONV_WIDE"); force = e ? atoi(e) : -1; }
     const size_t full = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(Cin * 2, 2);
     const bool big3x3 = kh == 3 && Cin == 128 && Cout >= 256;      // 256 rows per workgroup: 4 M-tiles per B fragment
     bool use = full > 160 * 1024 || Cin > 128 || (kh == 3 && Cin >= 64 && Cout <= 128) || (kh == 1 && Cin == 64 && Cout == 32) || big3x3;
-    if (force >= 0) use = force != 0;
     if (head_pf && !(big3x3 || (kh == 3 && Cin % 64 == 0 && Cin >= 128 && W >= 256))) use = false;   // the chunked tiles below have 256 rows only there
     // 3x3 layers with >= 128 channels on both sides: 256-position tiles (8 column blocks per wave: one weight fragment feeds
     // 8 MFMAs) with 64-channel chunks measured 6-13 % faster than 128-position tiles; the k15 layers measured slower
     const bool nb8 = kh == 3 && Cin % 64 == 0 && Cin >= 128 && Cout >= 128 && W >= 256;
-    // 4-wave form of the 256-row tile (MV_DCONV_W4=0 switches it off): 256 rows x 128 positions, 64-channel chunks, TWO workgroups per CU - one's
+    // 4-wave form of the 256-row tile: 256 rows x 128 positions, 64-channel chunks, TWO workgroups per CU - one's
     // staging and epilogue run under the other's MFMAs; every wave keeps the 64 x 128 tile of the 8-wave kernel
-    static int w4 = -1;
-    if (w4 < 0) { const char* e = getenv("MV_DCONV_W4"); w4 = e ? atoi(e) : 1; }
-    if (w4 && kh == 3 && Cin % 64 == 0 && Cout % 256 == 0 && W >= 128 && force != 0) {
+    if (kh == 3 && Cin % 64 == 0 && Cout % 256 == 0 && W >= 128) {
       p.cchunk = 64;
       const size_t xb = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(64 * 2, 2);
       const size_t ob = (size_t)128 * (256 * 2 + 16);
@@ -1419,11 +1394,8 @@ static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias
       return MV_OK;
     }
     // 128-row outputs of the big 3x3 layers (the data gradient of 128->256): 2 waves per workgroup, each with the 64 x 128 tile;
-    // 32-channel chunks keep the tile at 37 KB, so FOUR workgroups share a CU (445 -> 425 us; 64 input channels measured slower).
-    // MV_DCONV_W2 = smallest Cin that takes this path (0: never)
-    static int w2 = -1;
-    if (w2 < 0) { const char* e = getenv("MV_DCONV_W2"); w2 = e ? atoi(e) : 128; }
-    if (w2 && kh == 3 && Cin % 32 == 0 && Cin >= w2 && Cout == 128 && W >= 128 && force != 0) {
+    // 32-channel chunks keep the tile at 37 KB, so FOUR workgroups share a CU (445 -> 425 us; 64 input channels measured slower)
+    if (kh == 3 && Cin % 32 == 0 && Cin >= 128 && Cout == 128 && W >= 128) {
       p.cchunk = 32;
       const size_t xb = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(32 * 2, 2);
       const size_t ob = (size_t)128 * (128 * 2 + 16);
@@ -1470,13 +1442,8 @@ static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias
   }
   MV_DISPATCH(dtype, {
     hipStream_t s_ = (hipStream_t)stream;
-    static int m4 = -1;
-    if (m4 < 0) { const char* e = getenv("MV_DCONV_M4"); m4 = e ? atoi(e) : 1; }
-    if (Cout >= 256 && m4) {  // 4 waves x 64 rows: one B fragment feeds 4 MFMAs (LDS reads per MFMA halved), two workgroups per CU
+    if (Cout >= 256) {        // 4 waves x 64 rows: one B fragment feeds 4 MFMAs (LDS reads per MFMA halved), two workgroups per CU
       rc = dconv_launch<T, 4, 4, 8>(x, packed, bias, act_save, y, p, s_);
-    } else if (Cout >= 256) {        // 8 waves cover all 256 rows: the x tile is staged once per column block
-      rc = dconv_launch<T, 8, 2, 8>(x, packed, bias, act_save, y, p, s_);
-      if (rc == MV_ERR_UNSUPPORTED) rc = dconv_launch<T, 8, 2, 4>(x, packed, bias, act_save, y, p, s_);
     } else if (Cout >= 128) {
       rc = dconv_launch<T, 4, 2, 8>(x, packed, bias, act_save, y, p, s_);
       if (rc == MV_ERR_UNSUPPORTED) rc = dconv_launch<T, 4, 2, 4>(x, packed, bias, act_save, y, p, s_);
@@ -1597,23 +1564,23 @@ extern "C" size_t mv_dconv_wgrad_workspace_bytes(int Cin, int Cout, int kh, int 
   return sizeof(float) * (size_t)Cin * Cout * kh * kw;
 }
 
-template <typename T, int TH, int TW_, int WT>
+template <typename T, int TW_>
 static int dwgrad_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, int dil, hipStream_t s,
                          int xW = 0, long sample_stride = 0) {
+  constexpr int WT = 128;
   const int wsplit = cdiv(W, WT);
   const int halo = (TW_ - 1) * dil;
-  if (halo > (TH == 1 ? 64 : TW_ - 1)) return MV_ERR_UNSUPPORTED;
-  const size_t lds = 2 * (size_t)(WT + TH * (WT + halo)) * 160;
+  if (halo > 64) return MV_ERR_UNSUPPORTED;
+  const size_t lds = 2 * (size_t)(WT + (WT + halo)) * 160;
   if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
-  auto kern = dconv_wgrad_kernel<T, TH, TW_, WT>;
+  auto kern = dconv_wgrad_kernel<T, 1, TW_, WT>;
   static size_t lds_set = 0;
   if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
   const long nchunks = (long)B * H * wsplit;
   if (nchunks > (1L << 30)) return MV_ERR_UNSUPPORTED;
   const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
   // one workgroup per CU is resident (LDS); one round of workgroups keeps the final fp32 atomics to a few tens of MB
-  static int target = 0;
-  if (!target) { const char* e = getenv("MV_WGRAD_WGS"); target = e ? atoi(e) : 256; if (target < 1) target = 256; }
+  constexpr int target = 256;
   int groups = target / tiles; if (groups < 1) groups = 1; if (groups > nchunks) groups = (int)nchunks;
   int cpw = (int)((nchunks + groups - 1) / groups);
   if (sample_stride > 0) cpw = H * wsplit;            // one workgroup per (tile, sample)
@@ -1625,23 +1592,6 @@ static int dwgrad_launch(const void* x, const void* g, float* gws, float* gb, in
   return MV_OK;
 }
 
-#ifdef MV_DC_TIMING
-static void w3_dump(int mo, dim3 grid, hipStream_t st) {
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { (void)hipMalloc(&dbg, 4096 * 8 * 8); (void)hipMemcpyToSymbol(HIP_SYMBOL(dc_dbg), &dbg, sizeof(dbg)); return; }
-  if (++calls % 13 != 5) return;
-  (void)hipStreamSynchronize(st);
-  static long long hbuf[4096 * 8];
-  (void)hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-  const long nwg = (long)grid.x * grid.y * grid.z < 4096 ? (long)grid.x * grid.y * grid.z : 4096;
-  double avg[8] = {0}; int cnt[8] = {0};
-  for (long w = 0; w < nwg; ++w) for (int i = 0; i < 8; ++i) { long long v = hbuf[w * 8 + i]; if (v >= 0) { avg[i] += (double)v; cnt[i]++; } }
-  fprintf(stderr, "[wgrad3 timing] MO %d grid %u x %u x %u per chunk (issue+toff, bias, mfma, commit, barrier, chunks):", mo, grid.x, grid.y, grid.z);
-  for (int i = 0; i < 8; ++i) if (cnt[i]) fprintf(stderr, " %.0f", avg[i] / cnt[i]);
-  fprintf(stderr, "\n");
-}
-#endif
 template <typename T, int MO>
 static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, hipStream_t s) {
   constexpr int WT = 64, OT = 32 * MO;
@@ -1653,37 +1603,30 @@ static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, i
   const long nchunks = (long)B * wsplit * H;               // chunk = (sample, strip, row), rows fastest
   if (nchunks > (1L << 30) || (long)B * wsplit * (H + 2) > (1L << 30)) return MV_ERR_UNSUPPORTED;
   const int tiles = cdiv(Cin, 64) * cdiv(Cout, OT);
-  static int target = 0;
-  if (!target) { const char* e = getenv("MV_WGRAD_WGS"); target = e ? atoi(e) : 256; if (target < 1) target = 256; }
+  constexpr int target = 256;
   int groups = target / tiles; if (groups < 1) groups = 1; if (groups > nchunks) groups = (int)nchunks;
   const int cpw = (int)((nchunks + groups - 1) / groups);
   groups = (int)((nchunks + cpw - 1) / cpw);
   if (groups > 65535) return MV_ERR_UNSUPPORTED;
   dim3 grid(cdiv(Cin, 64), cdiv(Cout, OT), groups);
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const T*)x, (const T*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw);
-#ifdef MV_DC_TIMING
-  w3_dump(MO, grid, s);
-#endif
   return MV_OK;
 }
 
 template <typename T>
 static int dwgrad_dispatch(const void* x, const void* g, float* ws, float* gb, int B, int H, int W, int Cin, int Cout, int kh, int kw,
                            int dil, hipStream_t s) {
-  if (kh == 3 && kw == 3 && dil == 1) {
-    static int v3 = -1;
-    if (v3 < 0) { const char* e = getenv("MV_WGRAD3"); v3 = e ? atoi(e) : 1; }
-    if (v3) return Cout >= 128 ? dwgrad3_launch<T, 4>(x, g, ws, gb, B, H, W, Cin, Cout, s) : dwgrad3_launch<T, 2>(x, g, ws, gb, B, H, W, Cin, Cout, s);
-  }
-  if (kh == 3 && kw == 3) return dil == 1 ? dwgrad_launch<T, 3, 3, 64>(x, g, ws, gb, B, H, W, Cin, Cout, 1, s) : MV_ERR_UNSUPPORTED;
+  if (kh == 3 && kw == 3 && dil == 1)
+    return Cout >= 128 ? dwgrad3_launch<T, 4>(x, g, ws, gb, B, H, W, Cin, Cout, s) : dwgrad3_launch<T, 2>(x, g, ws, gb, B, H, W, Cin, Cout, s);
+  if (kh == 3 && kw == 3) return MV_ERR_UNSUPPORTED;
   if (kh != 1) return MV_ERR_UNSUPPORTED;
   switch (kw) {
-    case 1: return dwgrad_launch<T, 1, 1, 128>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 3: return dwgrad_launch<T, 1, 3, 128>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 5: return dwgrad_launch<T, 1, 5, 128>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 7: return dwgrad_launch<T, 1, 7, 128>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 11: return dwgrad_launch<T, 1, 11, 128>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 15: return dwgrad_launch<T, 1, 15, 128>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 1: return dwgrad_launch<T, 1>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 3: return dwgrad_launch<T, 3>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 5: return dwgrad_launch<T, 5>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 7: return dwgrad_launch<T, 7>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 11: return dwgrad_launch<T, 11>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 15: return dwgrad_launch<T, 15>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
     default: return MV_ERR_UNSUPPORTED;
   }
 }
@@ -1830,8 +1773,8 @@ extern "C" int mv_odconvT_wgrad_mfma(const void* x_cl, const void* gp, const voi
   MV_HIP(mvi_zero_async(tiles, sizeof(float) * (size_t)n * B, s));
   // "g" operand = x (rows = input channels), "x" operand = padded gradient rows (columns = (r, o)), taps q = 0, 1
   int rc;
-  if (dtype == MV_BF16) rc = dwgrad_launch<bf16, 1, 2, 128>(gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s, Tin + 1, n);
-  else rc = dwgrad_launch<f16, 1, 2, 128>(gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s, Tin + 1, n);
+  if (dtype == MV_BF16) rc = dwgrad_launch<bf16, 2>(gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s, Tin + 1, n);
+  else rc = dwgrad_launch<f16, 2>(gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s, Tin + 1, n);
   if (rc != MV_OK) return rc;
   const int g1 = (int)((n * K + 255) / 256 > 4096 ? 4096 : (n * K + 255) / 256);
   if (dtype == MV_BF16) hipLaunchKernelGGL(odconvT_tapmajor_kernel<bf16>, dim3(g1), dim3(256), 0, s, (const bf16*)w, (bf16*)wtm, n * K, Cin, Cout, ks, stride);

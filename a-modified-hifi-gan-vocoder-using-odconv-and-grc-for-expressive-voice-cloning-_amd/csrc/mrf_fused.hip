@@ -157,9 +157,6 @@ template <> struct Chunk<float> {
   static __device__ __forceinline__ u32x4 pack(const float* f) { return __builtin_bit_cast(u32x4, f32x4{f[0], f[1], f[2], f[3]}); }
 };
 
-#ifdef MV_MRF_TIMING
-__device__ long long* mrf_dbg = nullptr;
-#endif
 template <typename T, int NWAVES, int NTW, int PASS, bool STD>
 __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restrict__ x, StT<T>* __restrict__ out,
                                                           const char* __restrict__ packed, MrfMeta meta,
@@ -218,14 +215,6 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
   const int col = lane & 15, g = lane >> 4;
   const int b = blockIdx.y, wg = blockIdx.x;
   const int H = meta.halo;
-#ifdef MV_MRF_TIMING
-  long long tmk[12]; int ntm = 0;
-  const long long t_abs0 = __builtin_amdgcn_s_memrealtime();      // 100 MHz, chip-wide: when this wave started
-#define MRF_TM() do { if (ntm < 12) tmk[ntm++] = clock64(); } while (0)
-  MRF_TM();
-#else
-#define MRF_TM() do {} while (0)
-#endif
   const int rows = (SHARED ? NWAVES * TW : TW) + 2 * H;                  // rows of one staged tile
   char* xw = xl + (size_t)wid * (SHARED ? TW : rows) * RS;              // row 0 of this wave's window (its first halo row)
   char* xs = SHARED ? xl : xw;                                           // base of the tile this thread helps to stage
@@ -365,7 +354,6 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
     st8[q * 2 + 1] = rsqrtf(var + eps);
   }
   __syncthreads();
-  MRF_TM();
 
   const float* b_conv = tab, *b_res = tab + 64, *b_fus = tab + 128;
   const float* g5 = tab + 192, *be5 = tab + 256, *g8 = tab + 320, *be8 = tab + 384;
@@ -388,7 +376,6 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
     const int t0 = tile_t0(it);
     if constexpr (SHARED && PASS != 6) { if (it > 0) __syncthreads(); }   // every wave is done reading the previous shared tile
     commit(stage_t0(it));           // this tile: registers -> LDS (chain A / F: + x' -> HBM)
-    MRF_TM();
     if (it + 1 < nit) issue(it + 1);
     if constexpr (PASS == 6) continue;
     if constexpr (SHARED) __syncthreads(); else __builtin_amdgcn_wave_barrier();
@@ -456,7 +443,6 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
       }
     }
 
-    MRF_TM();
     if (STATS_V) {
       // partial sums of v per GN(5,20) group: concat rows 16m+4g..+3 are exactly group 4m+g
 #pragma unroll
@@ -524,7 +510,6 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
         for (int n = 0; n < NTW; ++n) f[m][n] = M::mma(af[m], cb[n], f[m][n]);
     }
 
-    MRF_TM();
     if (STATS_F) {
       // partial sums of f per GN(8,64) group: rows 16m+4g+r -> group 2m + (g>>1)
 #pragma unroll
@@ -621,17 +606,7 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
       }
       __builtin_amdgcn_wave_barrier();
     }
-    MRF_TM();
   }
-#ifdef MV_MRF_TIMING
-  MRF_TM();
-  if (lane == 0 && mrf_dbg) {
-    long long* d = mrf_dbg + ((size_t)(PASS - 1) * 65536 + ((size_t)(b * nwg + wg) * NWAVES + wid)) * 12;
-    for (int i = 0; i < 10; ++i) d[i] = i < ntm ? tmk[i] - tmk[0] : -1;
-    d[10] = t_abs0;
-    d[11] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 
   if (STATS_V) {
 #pragma unroll
@@ -695,11 +670,6 @@ static int mrf_launch(const void* x, void* out, const void* packed, const MrfMet
   float* part5 = ws;
   float* part8 = ws + (size_t)B * nwg * 32;
   dim3 grid(nwg, B), block(NWAVES * 64);
-#ifdef MV_MRF_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { hipMalloc(&dbg, 6 * 65536 * 12 * 8); hipMemset(dbg, 0xff, 6 * 65536 * 12 * 8); hipMemcpyToSymbol(HIP_SYMBOL(mrf_dbg), &dbg, sizeof(dbg)); }
-#endif
   const bool stdm = mrf_meta_is_std(meta);
   auto k1 = stdm ? mrf_kernel<T, NWAVES, NTW, 1, true> : mrf_kernel<T, NWAVES, NTW, 1, false>;
   auto k2 = stdm ? mrf_kernel<T, NWAVES, NTW, 2, true> : mrf_kernel<T, NWAVES, NTW, 2, false>;
@@ -718,21 +688,6 @@ static int mrf_launch(const void* x, void* out, const void* packed, const MrfMet
                      nullptr, part8, nullptr, 1.f, Tn, nwg, nit, eps, (const ST*)nullptr, (const char*)nullptr);
   hipLaunchKernelGGL(k3, grid, block, lds, stream, (const ST*)x, (ST*)out, (const char*)packed, meta, part5, nullptr,
                      part8, nullptr, mask, mask_scale, Tn, nwg, nit, eps, (const ST*)nullptr, (const char*)nullptr);
-#ifdef MV_MRF_TIMING
-  if (++calls == 20) {
-    hipStreamSynchronize(stream);
-    static long long hbuf[3 * 65536 * 12];
-    hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-    const int nwv = B * nwg * NWAVES;
-    for (int ps = 0; ps < 3; ++ps) {
-      double avg[12] = {0}; int cnt[12] = {0};
-      for (int w = 0; w < nwv; ++w) for (int i = 0; i < 12; ++i) { long long v = hbuf[((size_t)ps * 65536 + w) * 12 + i]; if (v >= 0) { avg[i] += (double)v; cnt[i]++; } }
-      fprintf(stderr, "[mrf timing] pass %d (nwg %d nit %d) clock64 marks:", ps + 1, nwg, nit);
-      for (int i = 0; i < 12; ++i) if (cnt[i]) fprintf(stderr, " %.0f", avg[i] / cnt[i]);
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
   return MV_OK;
 }
 
@@ -798,20 +753,13 @@ static int mrf_chain_launch(const void* x, void* out, const void* const* packed,
   constexpr bool WIDE_OK = (M::ES == 4) && NTW == 1;
   const size_t lds_wide = (size_t)MRF_CONV_FRAGS * FS + MRF_TAB_FLOATS * 4 + (32 + 16) * 4 + (size_t)NWAVES * 32 * 4 +
                           ((size_t)NWAVES * 2 * 16 + 2 * hmax) * RS;
-  static int wide_env = -1;
-  if (wide_env < 0) { const char* e = getenv("MV_MRF_WIDE_STATS"); wide_env = e ? atoi(e) : 1; }   // bit 0: pass 1, bit 1: pass A
-  const bool wide = WIDE_OK && wide_env && nit >= 2 && nit % 2 == 0 && lds_wide <= 160 * 1024 && Tn % (NWAVES * 32) == 0;
-#ifdef MV_MRF_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { hipMalloc(&dbg, 6 * 65536 * 12 * 8); hipMemset(dbg, 0xff, 6 * 65536 * 12 * 8); hipMemcpyToSymbol(HIP_SYMBOL(mrf_dbg), &dbg, sizeof(dbg)); }
-#endif
+  const bool wide = WIDE_OK && nit >= 2 && nit % 2 == 0 && lds_wide <= 160 * 1024 && Tn % (NWAVES * 32) == 0;
   const ST* xi = (const ST*)x;                       // x_i: the input of block i
   for (int i = 0; i < nblocks; ++i) {
     const bool stdm = mrf_meta_is_std(metas[i]);
     const char* pk = (const char*)packed[i];
     if (i == 0) {
-      if (wide && (wide_env & 1))
+      if (wide)
         mrf_chain_pass<T, NWAVES, (WIDE_OK ? 2 : NTW), 1>(stdm, grid, lds_wide, stream, xi, (ST*)nullptr, pk, metas[i], nullptr, part5, nullptr,
                                                           nullptr, Tn, nwg, nit / 2, eps, nullptr, nullptr);
       else
@@ -819,45 +767,15 @@ static int mrf_chain_launch(const void* x, void* out, const void* const* packed,
                                           nit, eps, nullptr, nullptr);
     } else {
       ST* xn = xbuf[i & 1];                          // pass A: x_i = GN8_{i-1}(f_{i-1}) + x_{i-1}, written once; statistics of v_i
-      if (wide && (wide_env & 2))      // (pass A at 32-step tiles needs 256 VGPRs + spills: 50 vs 43 us - off by default)
-        mrf_chain_pass<T, NWAVES, (WIDE_OK ? 2 : NTW), 4>(stdm, grid, lds_wide, stream, xi, xn, pk, metas[i], nullptr, part5, part8, nullptr,
-                                                          Tn, nwg, nit / 2, eps, fbuf, (const char*)packed[i - 1]);
-      else
-        mrf_chain_pass<T, NWAVES, NTW, 4>(stdm, grid, lds, stream, xi, xn, pk, metas[i], nullptr, part5, part8, nullptr, Tn, nwg, nit, eps,
-                                          fbuf, (const char*)packed[i - 1]);
+      // (pass A at 32-step tiles needs 256 VGPRs + spills: 50 vs 43 us)
+      mrf_chain_pass<T, NWAVES, NTW, 4>(stdm, grid, lds, stream, xi, xn, pk, metas[i], nullptr, part5, part8, nullptr, Tn, nwg, nit, eps,
+                                        fbuf, (const char*)packed[i - 1]);
       xi = xn;
     }
     // pass B: stages 1-3 once, f_i -> fbuf, statistics of f_i
     mrf_chain_pass<T, NWAVES, NTW, 5>(stdm, grid, lds, stream, xi, fbuf, pk, metas[i], part5, nullptr, nullptr, part8, Tn, nwg, nit, eps,
                                       nullptr, nullptr);
   }
-#ifdef MV_MRF_TIMING
-  {
-    const char* e = getenv("MV_MRF_TIMING_CALL");
-    if (++calls == (e ? atoi(e) : 30)) {
-      hipStreamSynchronize(stream);
-      static long long hbuf[6 * 65536 * 12];
-      hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-      for (int ps = 0; ps < 6; ++ps) {
-        double avg[10] = {0}; int cnt[10] = {0};
-        long long tmin = -1, tmax = -1, smax = -1;
-        for (int w = 0; w < 65536; ++w) {
-          const long long* d = hbuf + ((size_t)ps * 65536 + w) * 12;
-          if (d[0] < 0) continue;
-          for (int k = 0; k < 10; ++k) if (d[k] >= 0) { avg[k] += (double)d[k]; cnt[k]++; }
-          if (tmin < 0 || d[10] < tmin) tmin = d[10];
-          if (d[10] > smax) smax = d[10];
-          if (d[11] > tmax) tmax = d[11];
-        }
-        if (!cnt[0]) continue;
-        fprintf(stderr, "[mrf chain timing] pass %d nwg %d nit %d waves %d: span %.2f us (last start +%.2f us) marks:", ps + 1, nwg, nit, cnt[0],
-                (tmax - tmin) / 100.0, (smax - tmin) / 100.0);
-        for (int k = 0; k < 10; ++k) if (cnt[k]) fprintf(stderr, " %.0f", avg[k] / cnt[k]);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
-#endif
   if (ab_out) {
     constexpr size_t WB = (size_t)(MRF_CONV_FRAGS + MRF_RES_FRAGS + MRF_FUS_FRAGS) * FS;
     const float* tabp = reinterpret_cast<const float*>((const char*)packed[nblocks - 1] + WB);
@@ -890,22 +808,8 @@ extern "C" size_t mv_mrf_packed_bytes(int dtype) {
 // tile geometry per storage type: bf16/f16: 8 waves x 64 steps; fp32 (split operands, 2x LDS): 8 x 16 or 4 x 32 steps
 static inline bool mrf_fp32_storage(int dtype) { return dtype == MV_F32 || dtype == MV_F32_W16; }
 static inline int mrf_tile_t(int dtype) { return dtype == MV_F32_W16 ? 4 * 1 * 16 : dtype == MV_F32 ? 8 * 1 * 16 : 8 * 4 * 16; }
-// f32w16 wave tile: 16 or 32 steps (MV_MRF_W16_NTW=1|2; the single-f16 weight image is 48 KB, so a 256-step shared tile fits)
-static inline int mrf_w16_stream() {     // MV_MRF_STREAM=0: the tile form for MV_F32_W16 (A/B measurements)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MV_MRF_STREAM"); v = e ? atoi(e) : 1; }
-  return v;
-}
-static inline int mrf_w16_nw() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MV_MRF_W16_NW"); v = (e && atoi(e) == 4) ? 4 : (e && atoi(e) == 16) ? 16 : 8; }
-  return v;
-}
-static inline int mrf_w16_ntw() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MV_MRF_W16_NTW"); v = (e && atoi(e) == 1) ? 1 : 2; }
-  return v;
-}
+// f32w16 tile form (chains the streaming form does not take): 8 waves x 32 steps (the single-f16 weight image is 48 KB, so a
+// 256-step shared tile fits)
 
 extern "C" size_t mv_mrf_workspace_bytes(int B, int T_, int dtype) {
   const int ntiles = cdiv(T_, mrf_tile_t(dtype));   // upper bound on workgroups per sample
@@ -1002,15 +906,12 @@ extern "C" int mv_mrf_chain_out_fwd_cl(const void* x, void* wave, const void* co
         rc = mrf_chain_launch<float, 4, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_, fold ? &p8 : nullptr, &tb8, &nwg8);
       break;
     case MV_F32_W16: {
-      if (mrf_w16_stream() && fold && all_std) {     // streaming form (mrf_stream.hip)
+      if (fold && all_std) {     // streaming form (mrf_stream.hip)
         rc = mvi_mrf_chain_stream(x, nullptr, packed, nblocks, ws, mrf_act_bytes(B, T_, 4), B, T_, eps, st, &fl, &xl_, &x_pair, &p8, &tb8, &nwg8, x_pair_in);
         if (rc != MV_ERR_UNSUPPORTED) break;
       }
       if (x_pair_in) return MV_ERR_UNSUPPORTED;      // (the tile form reads fp32 rows)
-      const int cfg = mrf_w16_nw() * 10 + mrf_w16_ntw();
-#define MV_W16_CHAIN(NW_, NTW_) mrf_chain_launch<f32w16, NW_, NTW_>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_, fold ? &p8 : nullptr, &tb8, &nwg8)
-      rc = cfg == 82 ? MV_W16_CHAIN(8, 2) : cfg == 81 ? MV_W16_CHAIN(8, 1) : cfg == 42 ? MV_W16_CHAIN(4, 2) : cfg == 161 ? MV_W16_CHAIN(16, 1) : MV_W16_CHAIN(4, 1);
-#undef MV_W16_CHAIN
+      rc = mrf_chain_launch<f32w16, 8, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_, fold ? &p8 : nullptr, &tb8, &nwg8);
       break;
     }
     case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_); break;
@@ -1066,17 +967,14 @@ extern "C" int mv_mrf_chain_fwd_cl(const void* x, void* out, const void* const* 
     case MV_F32_W16: {
       bool all_std = true;
       for (int i = 0; i < nblocks; ++i) all_std = all_std && mrf_meta_is_std(metas[i]);
-      if (mrf_w16_stream() && all_std) {
+      if (all_std) {
         const void* fl = nullptr; const void* xl_ = nullptr; int xp = 0, nw = 0; const float* p8 = nullptr; const float* tb = nullptr;
         rc = mvi_mrf_chain_stream(x, out, packed, nblocks, ws, mrf_act_bytes(B, T_, 4), B, T_, eps, st, &fl, &xl_, &xp, &p8, &tb, &nw, x_pair_in);
         if (rc != MV_ERR_UNSUPPORTED) break;
       }
       if (x_pair_in) return MV_ERR_UNSUPPORTED;
-      const int cfg = mrf_w16_nw() * 10 + mrf_w16_ntw();
-#define MV_W16_CHAIN(NW_, NTW_) (out ? mrf_chain_launch<f32w16, NW_, NTW_>(x, out, packed, metas, nblocks, ws, B, T_, eps, st) \
-                                     : mrf_chain_launch<f32w16, NW_, NTW_>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_))
-      rc = cfg == 82 ? MV_W16_CHAIN(8, 2) : cfg == 81 ? MV_W16_CHAIN(8, 1) : cfg == 42 ? MV_W16_CHAIN(4, 2) : cfg == 161 ? MV_W16_CHAIN(16, 1) : MV_W16_CHAIN(4, 1);
-#undef MV_W16_CHAIN
+      rc = out ? mrf_chain_launch<f32w16, 8, 2>(x, out, packed, metas, nblocks, ws, B, T_, eps, st)
+               : mrf_chain_launch<f32w16, 8, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_);
       break;
     }
     case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(x, out, packed, metas, nblocks, ws, B, T_, eps, st); break;

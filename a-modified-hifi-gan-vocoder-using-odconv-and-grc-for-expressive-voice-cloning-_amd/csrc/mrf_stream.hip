@@ -51,16 +51,9 @@ struct SrArgs {
   const float* part8_in; float* part8_out;
   int Tn, L, nwg;
   float eps;
-  int dbg;                   // ablation switches of the MV_SR_TIMING build (bit 0: no f stores, bit 1: no stages 2-3, bit 2: no compute)
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
-#ifdef MV_SR_TIMING
-__device__ long long* sr_dbg = nullptr;     // [mode][wave][8]: wait, stage 1, stages 2-3 + stores, fill / dma issue, total, t_start, t_end (100 MHz)
-#define SR_TM(slot) do { const long long t_ = clock64(); tacc[slot] += t_ - tlast; tlast = t_; } while (0)
-#else
-#define SR_TM(slot) do {} while (0)
-#endif
 
 // HL: the streams between the blocks (x' and f) are hl8 rows (mfma.h) instead of pair / fp32 rows.  Then F0 writes f as hl8, A reads
 // f as hl8 and x as fp32 rows (XPAIR false: block 1) or hl8 rows (XPAIR true) and writes x' as hl8, F reads x' through registers
@@ -99,12 +92,6 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
   const int nt = span > 0 ? (span + 15) >> 4 : 0;               // column tiles of this wave
   const int nb = nt > 0 ? nt + 1 : 0;                           // 16-row batches: batch k = rows s0 - 5 + 16 k ..
   const int ring = (int)(rings - lds) + wid * SR_RING;          // LDS byte offset of this wave's ring
-#ifdef MV_SR_TIMING
-  long long tacc[5] = {0, 0, 0, 0, 0};
-  const long long t_abs0 = __builtin_amdgcn_s_memrealtime();
-  long long tlast = clock64();
-  const long long tfirst = tlast;
-#endif
 
   const size_t sample = (size_t)b * Tn * XRB;                 // of x
   const size_t sample_f = (size_t)b * Tn * FRB;               // of f (in or out)
@@ -372,7 +359,6 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
       f32x4 v[4];
       VB xb0[2];
       stage1(uc, v, xb0, nothing);
-      SR_TM(1);
       const int t0 = s0 + 16 * j;
       if (t0 + 16 <= Tn) {
 #pragma unroll
@@ -399,18 +385,12 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
         // V0 on pair rows: batches 0-2 were requested in the prologue; tile j needs batches j and j + 1, and the only thing requested
         // after them is DMA(j + 2) (5 instructions; nothing is stored in this pass).  Slot j % 3 is free behind the tile: batch j + 3.
         if (j + 2 < nb) asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SR_TM(0);
         tile(uc, j);
-        SR_TM(2);
         if (j + 3 < nb) dma(j + 3, U);
-        SR_TM(3);
       } else {
         if (j + 2 < nb) fill_issue(j + 2);              // in flight under this tile's MFMAs
-        SR_TM(0);
         tile(uc, j);
-        SR_TM(2);
         if (j + 2 < nb) fill_commit(j + 2, (U + 2) % 3);
-        SR_TM(3);
       }
     };
     for (int j = 0; j < nt; j += 3) {
@@ -534,15 +514,11 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
             } else {
               if (j + 3 < nb) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             }
-            SR_TM(0);
             stage1(un, vn, xb0n, piece);
-            SR_TM(1);
             if (j + 4 < nb) dma(j + 4, UN);
             rotate();
-            SR_TM(3);
           } else {
             finish_only();
-            SR_TM(2);
           }
         };
         for (int j = 0; j < nt; j += 3) {
@@ -560,15 +536,11 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
           jcur = j;
           if (j + 1 < nt) {
             if (j + 3 < nb) fill_issue(j + 3);        // in flight under this iteration's MFMAs
-            SR_TM(0);
             stage1(un, vn, xb0n, piece);
-            SR_TM(1);
             if (j + 3 < nb) fill_commit(j + 3, (UN + 2) % 3);     // slot j % 3: batch j is dead (stage 1 of tile j ran an iteration ago)
             rotate();
-            SR_TM(3);
           } else {
             finish_only();
-            SR_TM(2);
           }
         };
         for (int j = 0; j < nt; j += 3) {
@@ -580,16 +552,6 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
     }
   }
 
-#ifdef MV_SR_TIMING
-  if (lane == 0 && sr_dbg) {
-    long long* d = sr_dbg + ((size_t)MODE * 65536 + ((size_t)(b * nwg + wg) * SR_NW + wid)) * 8;
-    for (int i = 0; i < 4; ++i) d[i] = tacc[i];
-    d[4] = clock64() - tfirst;
-    d[5] = t_abs0;
-    d[6] = __builtin_amdgcn_s_memrealtime();
-    d[7] = nt;
-  }
-#endif
   // ---- statistics: lanes -> wave -> workgroup (fixed order), one partial per workgroup
   if constexpr (!FULL) {
 #pragma unroll
@@ -723,24 +685,15 @@ int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, in
   if ((size_t)Tn * SR_ROWB >= (1ull << 31)) return MV_ERR_UNSUPPORTED;     // 32-bit buffer offsets
   int L, nwg;
   sr_geometry(B, Tn, &L, &nwg);
-#ifdef MV_SR_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { (void)hipMalloc(&dbg, 4 * 65536 * 8 * 8); (void)hipMemset(dbg, 0xff, 4 * 65536 * 8 * 8); (void)hipMemcpyToSymbol(HIP_SYMBOL(sr_dbg), &dbg, sizeof(dbg)); }
-#endif
   float* fbuf = reinterpret_cast<float*>(ws);
   char* xbuf[2] = {ws + act_bytes, ws + 2 * act_bytes};
   float* part5 = reinterpret_cast<float*>(ws + 3 * act_bytes);
   float* part8 = part5 + (size_t)B * nwg * 32;
   SrArgs a{};
   a.Tn = Tn; a.L = L; a.nwg = nwg; a.eps = eps;
-  { const char* e = getenv("MV_SR_DBG"); a.dbg = e ? atoi(e) : 0; }
   const void* xi = x;
   bool xi_pair = x_pair_in != 0;               // the producer already wrote pair rows (the last upsampler's streaming kernel)
-  // hl8 rows between the blocks (MV_MRF_HL8=0: the 256-byte pair / fp32 rows of the first streaming form; pair-row input keeps them)
-  static int hl_env = -1;
-  if (hl_env < 0) { const char* e = getenv("MV_MRF_HL8"); hl_env = e ? atoi(e) : 1; }
-  const bool hl = hl_env != 0 && !xi_pair;
+  const bool hl = !xi_pair;                   // hl8 rows between the blocks (pair-row input keeps pair rows)
   for (int i = 0; i < nblocks; ++i) {
     a.packed = (const char*)packed[i];
     if (i == 0) {
@@ -749,46 +702,19 @@ int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, in
       if (xi_pair) sr_launch<SM_V0, true>(a, B, stream); else sr_launch<SM_V0, false>(a, B, stream);
       a.out = fbuf; a.part5_in = part5; a.part5_out = nullptr; a.part8_out = part8;
       if (xi_pair) sr_launch<SM_F, true>(a, B, stream);
-      else if (hl) sr_launch<SM_F0, false, true>(a, B, stream);
-      else sr_launch<SM_F0, false>(a, B, stream);
+      else sr_launch<SM_F0, false, true>(a, B, stream);
     } else {
       char* xn = xbuf[i & 1];
       a.x = xi; a.fprev = fbuf; a.out = xn; a.packed_prev = (const char*)packed[i - 1];
       a.part5_in = nullptr; a.part5_out = part5; a.part8_in = part8; a.part8_out = nullptr;
       if (hl) { if (xi_pair) sr_launch<SM_A, true, true>(a, B, stream); else sr_launch<SM_A, false, true>(a, B, stream); }
-      else if (xi_pair) sr_launch<SM_A, true>(a, B, stream);
-      else sr_launch<SM_A, false>(a, B, stream);
+      else sr_launch<SM_A, true>(a, B, stream);
       xi = xn; xi_pair = true;
       a.x = xi; a.fprev = nullptr; a.out = fbuf; a.packed_prev = nullptr;
       a.part5_in = part5; a.part5_out = nullptr; a.part8_in = nullptr; a.part8_out = part8;
       if (hl) sr_launch<SM_F, true, true>(a, B, stream); else sr_launch<SM_F, true>(a, B, stream);
     }
   }
-#ifdef MV_SR_TIMING
-  {
-    const char* e = getenv("MV_MRF_TIMING_CALL");
-    if (++calls == (e ? atoi(e) : 30)) {
-      (void)hipStreamSynchronize(stream);
-      static long long hbuf[4 * 65536 * 8];
-      (void)hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-      for (int md = 0; md < 4; ++md) {
-        double av[5] = {0}; int cnt = 0; long long tmin = -1, tmax = -1, smax = -1;
-        for (int w = 0; w < 65536; ++w) {
-          const long long* d = hbuf + ((size_t)md * 65536 + w) * 8;
-          if (d[4] < 0 || d[7] <= 0) continue;
-          for (int k = 0; k < 5; ++k) av[k] += (double)d[k];
-          ++cnt;
-          if (tmin < 0 || d[5] < tmin) tmin = d[5];
-          if (d[5] > smax) smax = d[5];
-          if (d[6] > tmax) tmax = d[6];
-        }
-        if (!cnt) continue;
-        fprintf(stderr, "[mrf stream timing] mode %d L %d nwg %d waves %d: span %.2f us (last start +%.2f us); per wave cycles: wait %.0f stage1 %.0f stage23+store %.0f fill/dma %.0f total %.0f\n",
-                md, L, nwg, cnt, (tmax - tmin) / 100.0, (smax - tmin) / 100.0, av[0] / cnt, av[1] / cnt, av[2] / cnt, av[3] / cnt, av[4] / cnt);
-      }
-    }
-  }
-#endif
   const float* tabp = reinterpret_cast<const float*>((const char*)packed[nblocks - 1] + SR_WB_ALL);
   if (out) {
     const long items = (long)Tn * 8;
@@ -797,15 +723,13 @@ int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, in
       hipLaunchKernelGGL((mrf_stream_final_kernel<true, true>), dim3(gx, B), dim3(256), 0, stream, fbuf, xi, part8, tabp, (float*)out, Tn, nwg, eps);
     else if (hl)
       hipLaunchKernelGGL((mrf_stream_final_kernel<false, true>), dim3(gx, B), dim3(256), 0, stream, fbuf, xi, part8, tabp, (float*)out, Tn, nwg, eps);
-    else if (xi_pair)
-      hipLaunchKernelGGL((mrf_stream_final_kernel<true, false>), dim3(gx, B), dim3(256), 0, stream, fbuf, xi, part8, tabp, (float*)out, Tn, nwg, eps);
     else
-      hipLaunchKernelGGL((mrf_stream_final_kernel<false, false>), dim3(gx, B), dim3(256), 0, stream, fbuf, xi, part8, tabp, (float*)out, Tn, nwg, eps);
+      hipLaunchKernelGGL((mrf_stream_final_kernel<true, false>), dim3(gx, B), dim3(256), 0, stream, fbuf, xi, part8, tabp, (float*)out, Tn, nwg, eps);
     return MV_OK;
   }
   // x_last_pair: 0 = x and f fp32 rows, 1 = x pair rows, 2 = x and f hl8 rows, 3 = x fp32 with f hl8 (one-block chain), 4 = x hl8, f fp32
   *f_last = fbuf; *x_last = xi;
-  *x_last_pair = !hl ? (xi_pair ? 1 : 0) : SR_FHL ? (xi_pair ? 2 : 3) : (xi_pair ? 4 : 0);
+  *x_last_pair = !hl ? 1 : SR_FHL ? (xi_pair ? 2 : 3) : (xi_pair ? 4 : 0);
   *part8_last = part8; *tab_last = tabp; *nwg_last = nwg;
   return MV_OK;
 }

@@ -98,12 +98,6 @@ __global__ __launch_bounds__(64) void odconv_attn_pooled_kernel(const float* __r
 // another 7 us of wave-tree reductions, 64-way LDS bank conflicts of the [C][T] tile read column-wise, and barriers.)
 constexpr int PRO_SG = 8;      // samples per FiLM workgroup
 constexpr int PRO_FI = 8;      // projection inputs per lane held in registers (cond_dim <= 64 * PRO_FI on the fast path)
-#ifdef MV_PRO_TIMING
-__device__ long long* pro_dbg = nullptr;
-#define PRO_TM() do { if (ntm < 8) tmk[ntm++] = clock64(); } while (0)
-#else
-#define PRO_TM() do {} while (0)
-#endif
 template <typename T, typename TI>
 __global__ __launch_bounds__(1024) void gen_prologue_kernel(const TI* __restrict__ mel, const T* __restrict__ att_w, const T* __restrict__ att_b,
                                                            const TI* __restrict__ spk, const TI* __restrict__ emo, const T* __restrict__ film_w,
@@ -112,10 +106,6 @@ __global__ __launch_bounds__(1024) void gen_prologue_kernel(const TI* __restrict
                                                            int C, int Tn, int K, int ds, int de, int cond_dim, int F2) {
   extern __shared__ float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nt = blockDim.x, nw = nt >> 6;
-#ifdef MV_PRO_TIMING
-  long long tmk[8]; int ntm = 0;
-#endif
-  PRO_TM();
 
   if ((int)blockIdx.x >= B) {
     // ---- FiLM role: rows j = rg * nw + wid, samples s0 .. s0 + PRO_SG
@@ -207,9 +197,7 @@ __global__ __launch_bounds__(1024) void gen_prologue_kernel(const TI* __restrict
     const long z1 = z0 + per < zero_n ? z0 + per : zero_n;
     for (long i = z0 + tid; i < z1; i += nt) zero_buf[i] = 0.f;
   }
-  PRO_TM();
   __syncthreads();
-  PRO_TM();
   // channels-last copy
   T* yb = x_cl + (long)b * Tn * C;
   for (int i = tid; i < C * Tn; i += nt) {
@@ -223,7 +211,6 @@ __global__ __launch_bounds__(1024) void gen_prologue_kernel(const TI* __restrict
     for (int t = part; t < Tn; t += P) a += xs[c * TP + t];
     psum[tid] = a;
   }
-  PRO_TM();
   __syncthreads();
   if (tid < C) {
     float a = 0.f;
@@ -231,7 +218,6 @@ __global__ __launch_bounds__(1024) void gen_prologue_kernel(const TI* __restrict
     mean[tid] = a / (float)Tn;
   }
   __syncthreads();
-  PRO_TM();
   // logits + softmax by wave 0 (odconv.py:37-40)
   if (wid == 0) {
     if (areg) {
@@ -269,10 +255,6 @@ __global__ __launch_bounds__(1024) void gen_prologue_kernel(const TI* __restrict
       if (lane < K) alpha[(long)b * K + lane] = e / den;
     }
   }
-#ifdef MV_PRO_TIMING
-  PRO_TM();
-  if (tid == 0 && pro_dbg) for (int i = 0; i < 8; ++i) pro_dbg[b * 8 + i] = i < ntm ? tmk[i] - tmk[0] : -1;
-#endif
 }
 
 // ---------------------------------------------------------------- GroupNorm
@@ -626,11 +608,6 @@ extern "C" int mv_gen_prologue_in(const void* mel, const void* att_w, const void
   const size_t lds = lds_sample > lds_film ? lds_sample : lds_film;
   if (lds > 64 * 1024) return MV_ERR_UNSUPPORTED;   // long inputs: the caller issues the separate launches
   const int n_film = film_proj ? ((F2 + NW - 1) / NW) * ((B + PRO_SG - 1) / PRO_SG) : 0;
-#ifdef MV_PRO_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { hipMalloc(&dbg, 1024 * 8 * 8); hipMemcpyToSymbol(HIP_SYMBOL(pro_dbg), &dbg, sizeof(dbg)); }
-#endif
   MV_DISPATCH(dtype, {
     if (in_dtype == dtype)
       hipLaunchKernelGGL((gen_prologue_kernel<T, T>), dim3(B + n_film), dim3(NT), lds, (hipStream_t)stream, (const T*)mel,
@@ -641,18 +618,6 @@ extern "C" int mv_gen_prologue_in(const void* mel, const void* att_w, const void
                          (const T*)att_w, (const T*)att_b, (const float*)spk, (const float*)emo, (const T*)film_w, (const T*)film_b,
                          alpha, (T*)x_cl, (T*)film_proj, zero_buf, zero_n, B, C, T_, K, ds, de, film_proj ? cond_dim : 0, F2);
   });
-#ifdef MV_PRO_TIMING
-  if (++calls == 2 && B <= 1024) {
-    hipStreamSynchronize((hipStream_t)stream);
-    static long long hbuf[1024 * 8];
-    hipMemcpy(hbuf, dbg, sizeof(long long) * 8 * B, hipMemcpyDeviceToHost);
-    double avg[8] = {0};
-    for (int w = 0; w < B; ++w) for (int i = 0; i < 8; ++i) avg[i] += (double)hbuf[w * 8 + i] / B;
-    fprintf(stderr, "[prologue timing] dtype %d marks (start, mel issued, film, sync1, copy, means+sync2, logits+softmax):", dtype);
-    for (int i = 0; i < 8; ++i) fprintf(stderr, " %.0f", avg[i]);
-    fprintf(stderr, "\n");
-  }
-#endif
   MV_LAUNCH_CHECK();
   return MV_OK;
 }

@@ -38,9 +38,6 @@ struct OdP {
   int pool_n;     // floats per sample in pooled_in: slots * rows partial sums of the producing launch (Cin = dense sums)
   int in_f16;     // fp32 launch whose INPUT x is fp16 (mixed storage: the first fp32 stage reads the fp16 stream; multi-tile kernel only)
   int out_pair;   // fp32 launch whose OUTPUT rows are written in the MRF chain's pair-row format (streaming kernel, 64 output channels)
-#ifdef MV_OD_TIMING
-  int dbg;        // ablation switches of the timing build (MV_KL_DBG)
-#endif
 };
 
 template <typename T> struct WLoad;   // this lane's 8 packed weights -> fp32
@@ -113,12 +110,6 @@ __global__ __launch_bounds__(256) void odconv_pack_kernel(const P* __restrict__ 
   }
 }
 
-#ifdef MV_OD_TIMING
-__device__ long long* od_dbg = nullptr;
-#define OD_TM() do { if (ntm < 8) tmk[ntm++] = clock64(); } while (0)
-#else
-#define OD_TM() do {} while (0)
-#endif
 // logits z[s][k] = Wa[k] . mean[s] + ba[k] from the channel sums in `scratch` (sample s at scratch + s * sstride): a wave takes two
 // (sample, bank) pairs at a time and issues ALL their attention-weight loads before the first multiply - a `for (c = lane; c < Cin;
 // c += 64) acc += w[c] * m[c]` loop is one L2 round trip per 64 channels (8 in a row for the first upsampler's 512: 12 k of its 70 k
@@ -228,7 +219,7 @@ __device__ __forceinline__ void od_logits(float* alds, const float* scratch, int
 template <typename T, int NTHR = 256>                     // NTHR: threads of the workgroup (those past 256 only take part in the logits)
 __device__ __forceinline__ void od_alpha_from_partials(float* alds, float* scratch, int S, int b0, const OdP& p,
                                                        const float* __restrict__ pooled_in, const T* __restrict__ att_w,
-                                                       const T* __restrict__ att_b, long long* tm = nullptr) {
+                                                       const T* __restrict__ att_b) {
   const int tid = threadIdx.x;
   const int Cin = p.Cin;
   const int npc = p.pool_n / Cin;                       // partials per channel
@@ -352,13 +343,10 @@ __device__ __forceinline__ void od_alpha_from_partials(float* alds, float* scrat
       for (int u = 0; u < 4; ++u)
         if (u0 + tid + 256 * u < E && tid < 256) scratch[u0 + tid + 256 * u] = a[u];       // [s][Cin]: needs S * Cin floats of scratch
     }
-    if (tm) tm[0] = clock64();
     __syncthreads();
-    if (tm) tm[1] = clock64();
-    if (fast) { fast_tail(Cin); if (tm) tm[2] = clock64(); return; }
+    if (fast) { fast_tail(Cin); return; }
     od_logits<T>(alds, scratch, Cin, S, p, att_w, att_b, havew, wpre, bpre);
   }
-  if (tm) tm[2] = clock64();
   __syncthreads();
   if (tid < S) {                                          // softmax over the banks, values in registers (one LDS round trip, not 3 K)
     float z[OD_MAXK], m = -INFINITY, den = 0.f;
@@ -452,10 +440,6 @@ __global__ __launch_bounds__(256) void odconv_cl_kernel(const T* __restrict__ x,
   char* xl = reinterpret_cast<char*>(bias_l + S * 4 * MW * 16);
   const int PLANE = p.Cin * LES;                               // byte offset of the lo plane inside a row (SPLIT)
   const int RS = lds_row_stride(SPLIT ? 2 * PLANE : p.Cin * ES, LES);
-#ifdef MV_OD_TIMING
-  long long tmk[8]; int ntm = 0;
-#endif
-  OD_TM();
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 15, g = lane >> 4;
@@ -474,7 +458,6 @@ __global__ __launch_bounds__(256) void odconv_cl_kernel(const T* __restrict__ x,
     od_alpha_from_partials<T>(alds, reinterpret_cast<float*>(xl), S, b0, p, pooled_in, att_w, att_b);   // xl: not staged yet
     __syncthreads();                                   // the scratch is dead before the x tiles land in it
   }
-  OD_TM();
   // ---- stage x tiles: input rows q0+shift_lo .. +nrows-1 of every sample, zero outside [0,Tin)
   {
     const int cpr = p.Cin * ES / 16;
@@ -519,7 +502,6 @@ __global__ __launch_bounds__(256) void odconv_cl_kernel(const T* __restrict__ x,
     }
   }
   __syncthreads();
-  OD_TM();
   // alpha-mixed bias of this workgroup's rows, once, into LDS: the K bank loads of a row are independent and overlap the first
   // weight fetch (read one at a time in the epilogue they were serialized L2 round trips)
   if (bias) {
@@ -618,7 +600,6 @@ __global__ __launch_bounds__(256) void odconv_cl_kernel(const T* __restrict__ x,
     while (c8 >= cpc) { c8 -= cpc; ++tap; }
   }
 
-  OD_TM();
   // ---- epilogue: bias, FiLM, activation -> LDS tile [s][q][rows of this workgroup] -> whole-row 16-byte stores
   __syncthreads();                                   // every wave is done with the x tiles: reuse the region
   constexpr int RW = 4 * MW * 16;                    // GEMM rows covered by this workgroup
@@ -696,7 +677,6 @@ __global__ __launch_bounds__(256) void odconv_cl_kernel(const T* __restrict__ x,
     else if (pooled_out) { if (simple) epilogue(al_, FF{}, TT{}); else epilogue(aa_, FF{}, TT{}); }
     else { if (simple) epilogue(al_, FF{}, FF{}); else epilogue(aa_, FF{}, FF{}); }
   }
-  OD_TM();
   __syncthreads();
   {
     constexpr int EPC = 16 / ES;                     // elements per 16-byte chunk
@@ -717,13 +697,6 @@ __global__ __launch_bounds__(256) void odconv_cl_kernel(const T* __restrict__ x,
         *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(y + ((long)b * p.Tout + u) * p.Cout + o)) = val;
       }
   }
-#ifdef MV_OD_TIMING
-  OD_TM();
-  if (tid == 0 && od_dbg) {
-    const long wgid = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (wgid < 8192) for (int i = 0; i < 8; ++i) od_dbg[wgid * 8 + i] = i < ntm ? tmk[i] - tmk[0] : -1;
-  }
-#endif
 }
 
 
@@ -995,8 +968,7 @@ static int od_mt_launch(const void* x, const void* wp, const void* bias, const f
   const int ntl = cdiv(p.nq, NB * 16);
   const int gy = cdiv(p.M / 16, 4 * MW);
   // about two workgroups per CU: enough to overlap each other's barriers, few enough to amortise the per-workgroup weight mix
-  static int tgt = -1;
-  if (tgt < 0) { const char* e = getenv("MV_OD_MT_WGS"); tgt = e ? atoi(e) : 512; }
+  constexpr int tgt = 512;
   int TL = (int)(((long)ntl * gy * p.B + tgt - 1) / tgt);
   if (TL < 1) TL = 1;
   if (TL > 16) TL = 16;
@@ -1039,10 +1011,6 @@ __global__ __launch_bounds__(512) void odconv_sample_kernel(const T* __restrict_
   const int b = blockIdx.y, n_mt = p.M / 16;
   const int mt = blockIdx.x * 8 + wid;                         // this wave's M-tile (host: M % 128 == 0)
   const int nrows = p.nq + 1;                                  // input steps shift_lo .. Tin (the first and the last are zeros)
-#ifdef MV_OD_TIMING
-  long long tmk[8]; int ntm = 0;
-#endif
-  OD_TM();
 
   // ---- bank fragments of the first RD k-steps: they depend on nothing
   const long bank_stride = (long)n_mt * KST * 512 * ES;
@@ -1075,7 +1043,6 @@ __global__ __launch_bounds__(512) void odconv_sample_kernel(const T* __restrict_
     for (int i = 0; i < RD; ++i) ldring(i, i);
     __builtin_amdgcn_sched_barrier(0);
   }
-  OD_TM();
   if (!fastalpha) {
     if (alpha_in) {
       if (tid < p.K) alds[tid] = alpha_in[(long)b * p.K + tid];
@@ -1083,11 +1050,9 @@ __global__ __launch_bounds__(512) void odconv_sample_kernel(const T* __restrict_
       od_alpha_from_partials<T, 512>(alds, ascr, 1, b, p, pooled_in, att_w, att_b);
     }
   }
-  OD_TM();
   static_assert(RD * KB == 16, "the counted wait below");
   if (fastalpha) { asm volatile("s_waitcnt vmcnt(16)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }   // rows landed (and alds written); ring in flight
   else { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
-  OD_TM();
   float al[KB];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) al[kb] = kb < p.K ? alds[kb] : 0.f;
@@ -1129,7 +1094,6 @@ __global__ __launch_bounds__(512) void odconv_sample_kernel(const T* __restrict_
     for (int n = 0; n < NT; ++n) acc[n] = M::mma(a, M::load_b(xl + lb[n] + koff), acc[n]);
   }
 
-  OD_TM();
   // ---- epilogue: bias, activation, 8-byte stores (a lane's 4 rows are 4 consecutive channels), channel sums for the next layer
   const ActLrelu actf{p.act == ACT_NONE ? 1.f : p.slope};
   float psum[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1157,13 +1121,6 @@ __global__ __launch_bounds__(512) void odconv_sample_kernel(const T* __restrict_
     }
     if (col == 0) *reinterpret_cast<f32x4*>(pooled_out + (long)b * p.M + row) = f32x4{psum[0], psum[1], psum[2], psum[3]};
   }
-#ifdef MV_OD_TIMING
-  OD_TM();
-  if (tid == 0 && od_dbg) {
-    const long wgid = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    if (wgid < 8192) for (int i = 0; i < 8; ++i) od_dbg[wgid * 8 + i] = i < ntm ? tmk[i] - tmk[0] : -1;
-  }
-#endif
 }
 
 template <typename T, int CIN, int NT>
@@ -1180,27 +1137,8 @@ static int od_sample_launch(const void* x, const void* wp, const void* bias, con
   dim3 grid(p.M / 128, p.B);
   if (grid.y > 65535) return MV_ERR_UNSUPPORTED;
   if (slots_out) { *slots_out = 1; return MV_OK; }
-#ifdef MV_OD_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { hipMalloc(&dbg, 8192 * 8 * 8); hipMemcpyToSymbol(HIP_SYMBOL(od_dbg), &dbg, sizeof(dbg)); }
-  hipMemsetAsync(dbg, 0xff, 8192 * 8 * 8, stream);
-#endif
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, (const T*)x, (const T*)wp, (const T*)bias, alpha, pooled_in,
                      (const T*)att_w, (const T*)att_b, (T*)y, pooled_out, p);
-#ifdef MV_OD_TIMING
-  if (++calls == 20) {
-    hipStreamSynchronize(stream);
-    static long long hbuf[8192 * 8];
-    hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-    const long nwg = (long)grid.x * grid.y;
-    double avg[8] = {0}; int cnt[8] = {0};
-    for (long w = 0; w < nwg; ++w) for (int i = 0; i < 8; ++i) { long long v = hbuf[w * 8 + i]; if (v >= 0) { avg[i] += (double)v; cnt[i]++; } }
-    fprintf(stderr, "[sample timing] grid %u x %u marks (start, issued, alpha, staged, loop, end):", grid.x, grid.y);
-    for (int i = 0; i < 8; ++i) if (cnt[i]) fprintf(stderr, " %.0f", avg[i] / cnt[i]);
-    fprintf(stderr, "\n");
-  }
-#endif
   return MV_OK;
 }
 
@@ -1261,31 +1199,22 @@ __global__ __launch_bounds__(256) void odconv_kloop_kernel(const T* __restrict__
   const int b0 = blockIdx.y * S;
   const int n_mt = p.M / 16;
   const int ZR = p.nrows - 1;                      // index of the all-zero row
-#ifdef MV_OD_TIMING
-  long long tmk[8]; int ntm = 0;
-#endif
-  OD_TM();
 
   // ---- 16-bit storage: the whole (short) input of the S samples goes to LDS by LDS-DMA, one 1 KB piece of a row per instruction, all
   // of them issued before anything else (no register round trip, no wait between batches); rows outside the sample and the zero row
   // fail the buffer range check and arrive as zeros.  In-kernel marks of the register-staged form at the first upsampler: attention
   // prologue 25.5 k ticks, THEN staging 14.1 k (three dependent batches), main loop 32.6 k, epilogue 8.4 k.
   constexpr bool XDMA = !SPLIT;
-#ifdef MV_OD_TIMING
-  const int kdbg = p.dbg;
-#else
-  constexpr int kdbg = 0;
-#endif
   // Attention on one wave per sample (the last S of the four waves; od_alpha_wave): no barrier, one round trip, requested ahead of the
   // staging traffic that the other waves issue.
   const int wu = __builtin_amdgcn_readfirstlane(wid);
-  const bool wavealpha = XDMA && !alpha_in && !kdbg && S <= 2 && p.K <= 4 && p.Cin <= 64 * OD_LU;
+  const bool wavealpha = XDMA && !alpha_in && S <= 2 && p.K <= 4 && p.Cin <= 64 * OD_LU;
   const int nstw = wavealpha ? 4 - S : 4;          // staging waves
   if (wavealpha && wu >= nstw) {
     const int s = wu - nstw;
     if (b0 + s < p.B) od_alpha_wave<T>(alds + s * OD_MAXK, b0 + s, p, pooled_in, att_w, att_b);
     else if (lane < OD_MAXK) alds[s * OD_MAXK + lane] = 0.f;
-  } else if (XDMA && !(kdbg & 1)) {
+  } else if (XDMA) {
     typedef __attribute__((address_space(3))) void lds_void;
     const int RB = p.Cin * ES;                     // bytes of one row
     const long xbytes = (long)p.B * p.Tin * RB;
@@ -1304,25 +1233,15 @@ __global__ __launch_bounds__(256) void odconv_kloop_kernel(const T* __restrict__
   }
   // ---- alpha (odconv.py:36-40)
   if (wavealpha) {
-    OD_TM(); OD_TM(); OD_TM(); OD_TM();
+    // (written by the attention waves above)
   } else if (alpha_in) {
     if (tid < S * p.K) {
       const int s = tid / p.K, kb = tid % p.K;
       alds[s * OD_MAXK + kb] = (b0 + s < p.B) ? alpha_in[(long)(b0 + s) * p.K + kb] : 0.f;
     }
-  } else if (kdbg & 2) {
-    if (tid < S * p.K) alds[(tid / p.K) * OD_MAXK + tid % p.K] = 0.25f;
-    OD_TM(); OD_TM(); OD_TM(); OD_TM();
   } else {
-#ifdef MV_OD_TIMING
-    OD_TM();
-    od_alpha_from_partials<T>(alds, ascr, S, b0, p, pooled_in, att_w, att_b, tmk + ntm);
-    ntm += 3;
-#else
     od_alpha_from_partials<T>(alds, ascr, S, b0, p, pooled_in, att_w, att_b);
-#endif
   }
-  OD_TM();
   // ---- stage the whole (short) input of every sample: row r <-> input step r + shift_lo, last row = zeros
   {
     const int cpr = p.Cin * ES / 16;               // 16-byte global pieces per row
@@ -1359,7 +1278,6 @@ __global__ __launch_bounds__(256) void odconv_kloop_kernel(const T* __restrict__
   }
   if constexpr (XDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  OD_TM();
 
   // out = sum_kb alpha[b,kb] * D_kb; D_kb lives in `acc` while bank kb streams and is folded into `out` at the end of the bank
   f32x4 acc[MW][S][NB], out[MW][S][NB];
@@ -1469,7 +1387,6 @@ __global__ __launch_bounds__(256) void odconv_kloop_kernel(const T* __restrict__
     }
   }
 
-  OD_TM();
   // ---- epilogue: bias, activation -> LDS tile [s][q][rows of this workgroup] -> whole-row stores
   __syncthreads();
   constexpr int RW = 64 * MW;
@@ -1553,13 +1470,6 @@ __global__ __launch_bounds__(256) void odconv_kloop_kernel(const T* __restrict__
         *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(y + ((long)b * p.Tout + u) * p.Cout + o)) = val;
       }
   }
-#ifdef MV_OD_TIMING
-  OD_TM();
-  if (tid == 0 && od_dbg) {
-    const long wgid = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    if (wgid < 8192) for (int i = 0; i < 8; ++i) od_dbg[wgid * 8 + i] = i < ntm ? tmk[i] - tmk[0] : -1;
-  }
-#endif
 }
 
 template <typename T, int S, int NB, int MW>
@@ -1585,32 +1495,12 @@ static int od_kloop_launch(const void* x, const void* wp, const void* bias, cons
   dim3 grid(cdiv(p.M / 16, 4 * MW), cdiv(p.B, S));
   if (grid.y > 65535) return MV_ERR_UNSUPPORTED;
   if (slots_out) { *slots_out = 1; return MV_OK; }
-#ifdef MV_OD_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { hipMalloc(&dbg, 8192 * 8 * 8); hipMemcpyToSymbol(HIP_SYMBOL(od_dbg), &dbg, sizeof(dbg)); }
-  hipMemsetAsync(dbg, 0xff, 8192 * 8 * 8, stream);
-  { const char* e = getenv("MV_KL_DBG"); p.dbg = e ? atoi(e) : 0; }
-#endif
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)x, (const T*)wp, (const T*)bias, alpha, pooled_in,
                      (const T*)att_w, (const T*)att_b, (T*)y, pooled_out, p);
-#ifdef MV_OD_TIMING
-  if (++calls == 20) {
-    hipStreamSynchronize(stream);
-    static long long hbuf[8192 * 8];
-    hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-    const long nwg = (long)grid.x * grid.y < 8192 ? (long)grid.x * grid.y : 8192;
-    double avg[8] = {0}; int cnt[8] = {0};
-    for (long w = 0; w < nwg; ++w) for (int i = 0; i < 8; ++i) { long long v = hbuf[w * 8 + i]; if (v >= 0) { avg[i] += (double)v; cnt[i]++; } }
-    fprintf(stderr, "[kloop timing] S %d MW %d grid %u x %u marks (start, dma issued, sums, barrier, logits, alpha, staged, loop | end):", S, MW, grid.x, grid.y);
-    for (int i = 0; i < 8; ++i) if (cnt[i]) fprintf(stderr, " %.0f", avg[i] / cnt[i]);
-    fprintf(stderr, "\n");
-  }
-#endif
   return MV_OK;
 }
 
-template <typename T, int S, int MW, int NB, bool PFW, int KB>
+template <typename T, int S, int MW, int NB, int KB>
 static int od_launch(const void* x, const void* wp, const void* bias, const float* alpha, const float* pooled_in,
                      const void* att_w, const void* att_b, const void* film, void* y, float* pooled_out, OdP p,
                      hipStream_t stream, int* slots_out) {
@@ -1620,7 +1510,7 @@ static int od_launch(const void* x, const void* wp, const void* bias, const floa
   const size_t obytes = (size_t)S * NB * 16 * (4 * MW * 16 * M::ES + 16);    // staged output tile reuses the x region
   const size_t lds = sizeof(float) * (S * OD_MAXK + S * 4 * MW * 16) + (xbytes > obytes ? xbytes : obytes);
   if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
-  auto kern = odconv_cl_kernel<T, S, MW, NB, (PFW && (M::ES == 2 || MW * NB <= 3)), KB>;   // fp32: prefetch only in the small (input_proj) instantiation
+  auto kern = odconv_cl_kernel<T, S, MW, NB, (M::ES == 2 || MW * NB <= 3), KB>;   // fp32: prefetch only in the small (input_proj) instantiation
   static size_t lds_set = 0;
   if (lds > lds_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1629,27 +1519,8 @@ static int od_launch(const void* x, const void* wp, const void* bias, const floa
   dim3 grid(cdiv(p.nq, NB * 16), cdiv(p.M / 16, 4 * MW), cdiv(p.B, S));
   if (grid.y > 65535 || grid.z > 65535) return MV_ERR_UNSUPPORTED;
   if (slots_out) { *slots_out = (int)grid.x; return MV_OK; }
-#ifdef MV_OD_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { hipMalloc(&dbg, 8192 * 8 * 8); hipMemcpyToSymbol(HIP_SYMBOL(od_dbg), &dbg, sizeof(dbg)); }
-  hipMemsetAsync(dbg, 0xff, 8192 * 8 * 8, stream);
-#endif
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)x, (const T*)wp, (const T*)bias, alpha, pooled_in,
                      (const T*)att_w, (const T*)att_b, (const T*)film, (T*)y, pooled_out, p);
-#ifdef MV_OD_TIMING
-  if (++calls == 20) {
-    hipStreamSynchronize(stream);
-    static long long hbuf[8192 * 8];
-    hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-    const long nwg = (long)grid.x * grid.y * grid.z < 8192 ? (long)grid.x * grid.y * grid.z : 8192;
-    double avg[8] = {0}; int cnt[8] = {0};
-    for (long w = 0; w < nwg; ++w) for (int i = 0; i < 8; ++i) { long long v = hbuf[w * 8 + i]; if (v >= 0) { avg[i] += (double)v; cnt[i]++; } }
-    fprintf(stderr, "[od timing] Cin %d M %d ksteps %d grid %u x %u x %u marks:", p.Cin, p.M, p.ksteps, grid.x, grid.y, grid.z);
-    for (int i = 0; i < 8; ++i) if (cnt[i]) fprintf(stderr, " %.0f", avg[i] / cnt[i]);
-    fprintf(stderr, "\n");
-  }
-#endif
   return MV_OK;
 }
 
@@ -1736,12 +1607,6 @@ extern "C" int mv_odconv_cl_pack(const void* kernels, int param_dtype, void* pac
 // A wave writes all M rows of its columns (M / Cout whole output rows per input column).
 constexpr int OS_NW = 8, OS_RB = 256, OS_RS = OS_RB + 16, OS_SLOT = 16 * OS_RS, OS_RING = 2 * OS_SLOT + OS_RS;
 constexpr float OS_WSCALE = 64.f, OS_WUNSCALE = 1.f / 64.f;
-#ifdef MV_OS_TIMING
-__device__ long long* os_dbg = nullptr;   // [wave][8]: alpha, bias + aggregation, first fill, tiles (compute), tiles (carry + commit), pooled, total
-#define OS_TM(slot) do { const long long t_ = clock64(); tacc[slot] += t_ - tlast; tlast = t_; } while (0)
-#else
-#define OS_TM(slot) do {} while (0)
-#endif
 
 template <int CIN, int MT, bool XF16>
 __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* __restrict__ x, const float* __restrict__ wp,
@@ -1763,11 +1628,6 @@ __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* _
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.z, R0 = blockIdx.y * MT * 16, n_mt = p.M / 16;
   const int ring = (int)(rings - lds) + wid * OS_RING, carry = ring + 2 * OS_SLOT;
-#ifdef MV_OS_TIMING
-  long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long tlast = clock64();
-  const long long tfirst = tlast, t_abs0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // ---- this wave's span of input columns (the sample's last wave also takes the ragged end: nq = Tin + 1 leaves one column over)
   const int wave_id = blockIdx.x * OS_NW + wid;
@@ -1864,7 +1724,6 @@ __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* _
     }
     __syncthreads();
   }
-  OS_TM(0);
   if (!early && !wavealpha) { frag_loads(); first_rows(); }
   float al[KB];
 #pragma unroll
@@ -1894,7 +1753,6 @@ __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* _
     commit(ra, 0);
   }
   __syncthreads();
-  OS_TM(1);
 
   // B-operand bases of this lane: k-step ks -> chunk 4 ks + g -> (tap, 8-channel group); tap 0 reads row col of the tile's slot, tap 1
   // row col - 1 (column 0: the carry row = the last row of the previous batch)
@@ -1991,7 +1849,6 @@ __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* _
       constexpr int U = decltype(uc)::value;
       if (j + 2 < nt) issue(rfree, j + 2);
       tile(uc, j);
-      OS_TM(3);
       if (j + 1 < nt) {
         // the next tile's carry = the last row of this batch; then batch j + 1 lands in the other slot
         if (lane < 16) {
@@ -2000,23 +1857,12 @@ __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* _
         }
         commit(rnext, U ^ 1);
       }
-      OS_TM(4);
     };
     for (int j = 0; j < nt; j += 2) {
       step(std::integral_constant<int, 0>{}, j, rb, ra);
       if (j + 1 < nt) step(std::integral_constant<int, 1>{}, j + 1, ra, rb);
     }
   }
-#ifdef MV_OS_TIMING
-  if (lane == 0 && os_dbg) {
-    const long w = (((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * OS_NW + wid;
-    if (w < 65536) {
-      long long* d = os_dbg + w * 8;
-      for (int i = 0; i < 5; ++i) d[i] = tacc[i];
-      d[5] = clock64() - tfirst; d[6] = t_abs0; d[7] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
-#endif
 
   if (pooled_out) {                                      // one partial per (row, workgroup): slot blockIdx.x of this sample
 #pragma unroll
@@ -2056,35 +1902,8 @@ static int od_stream_launch(const void* x, const void* wp, const void* bias, con
   auto kern = odconv_stream_kernel<CIN, MT, XF16>;
   static bool set = false;
   if (!set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
-#ifdef MV_OS_TIMING
-  static long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { (void)hipMalloc(&dbg, 65536 * 8 * 8); (void)hipMemcpyToSymbol(HIP_SYMBOL(os_dbg), &dbg, sizeof(dbg)); }
-  (void)hipMemsetAsync(dbg, 0xff, 65536 * 8 * 8, stream);
-#endif
   hipLaunchKernelGGL(kern, dim3(gx, gy, p.B), dim3(OS_NW * 64), lds, stream, x, (const float*)wp, (const float*)bias, alpha, pooled_in,
                      (const float*)att_w, (const float*)att_b, (float*)y, pooled_out, p, tpw * 16);
-#ifdef MV_OS_TIMING
-  {
-    const char* e = getenv("MV_MRF_TIMING_CALL");
-    if (++calls == (e ? atoi(e) : 30)) {
-      (void)hipStreamSynchronize(stream);
-      static long long hbuf[65536 * 8];
-      (void)hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-      double av[6] = {0}; int cnt = 0; long long tmin = -1, tmax = -1;
-      for (int w = 0; w < 65536; ++w) {
-        const long long* d = hbuf + (size_t)w * 8;
-        if (d[5] < 0) continue;
-        for (int k = 0; k < 6; ++k) av[k] += (double)d[k];
-        ++cnt;
-        if (tmin < 0 || d[6] < tmin) tmin = d[6];
-        if (d[7] > tmax) tmax = d[7];
-      }
-      if (cnt) fprintf(stderr, "[od stream timing] Cin %d MT %d grid %d x %d x %d tpw %d waves %d: span %.2f us; per wave cycles: alpha %.0f bias+mix %.0f first fill %.0f tiles %.0f carry+commit %.0f total %.0f\n",
-                       CIN, MT, gx, gy, p.B, tpw, cnt, (tmax - tmin) / 100.0, av[0] / cnt, av[1] / cnt, av[2] / cnt, av[3] / cnt, av[4] / cnt, av[5] / cnt);
-    }
-  }
-#endif
   return MV_OK;
 }
 
@@ -2097,28 +1916,21 @@ static int od_dispatch(const void* x, const void* packed, const void* bias, cons
   const int ntiles = cdiv(p.nq, 16);
   const long wbytes = (long)K * p.M * p.ksteps * 32 * (dtype == MV_F32 ? 4 : 2);
   int rc = MV_ERR_DTYPE;
-  // with the unconditional (clamped) prefetch the prefetching instantiation wins for the short-K upsamplers as well
-  // (ups3 48 -> 44 us); MV_OD_PF=0 selects the non-prefetching one for comparison
-  static int force_pf = -1;
-  if (force_pf < 0) { const char* e = getenv("MV_OD_PF"); force_pf = e ? atoi(e) : 1; }
+  // with the unconditional (clamped) prefetch the prefetching instantiation wins for the short-K upsamplers as well (ups3 48 -> 44 us)
 #define OD_GO(S_, MW_, NB_) do { \
-    if (K <= 4 && p.ksteps <= 8 && !force_pf) rc = od_launch<T, S_, MW_, NB_, false, 4>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); \
-    else if (K <= 4) rc = od_launch<T, S_, MW_, NB_, true, 4>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); \
-    else rc = od_launch<T, S_, MW_, NB_, true, 8>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); } while (0)
+    if (K <= 4) rc = od_launch<T, S_, MW_, NB_, 4>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); \
+    else rc = od_launch<T, S_, MW_, NB_, 8>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); } while (0)
   if (p.in_f16 && (dtype != MV_F32 || ntiles <= 3 || wbytes > (1 << 20))) return MV_ERR_UNSUPPORTED;   // (only the multi-tile kernel below)
   if (p.out_pair && (dtype != MV_F32 || ntiles <= 3 || wbytes > (1 << 20) || p.Cout != 64 || p.in_f16)) return MV_ERR_UNSUPPORTED;   // (only the 64-channel streaming kernel)
   MV_DISPATCH(dtype, {
     if (ntiles <= 3) {                       // short sequences, big kernels (input_proj, first upsampler)
       rc = MV_ERR_UNSUPPORTED;
       if (!film_proj && wbytes > (4 << 20) && B >= 2)   // K-loop, weights-stationary over S samples
-      {   // S = 2 measured best; S = 1 if the tiles do not fit.  MV_KLOOP_MW selects the M-tiles per wave (A/B measurements)
+      {   // S = 2 measured best; S = 1 if the tiles do not fit.
         // measured at ups0 (C2): 16-bit 41.5 us with one M-tile per wave (two workgroups per CU) vs 43.8 with two; fp32 (split
         // operands, 3 MFMAs per product) 97 us with two M-tiles per wave vs 133 with one.  The launch is bound by the weight
         // stream out of L2 (16 sample groups x 16.8 MB = 268 MB), not by the matrix pipe (12 us) - see DESIGN.md
-        static int kmw = -1;
-        if (kmw < 0) { const char* e = getenv("MV_KLOOP_MW"); kmw = e ? atoi(e) : 0; }
-        const int mw_sel = kmw ? kmw : (dtype == MV_F32 ? 2 : 1);
-        if (mw_sel == 2) {   // (four samples per workgroup halve the L2 stream but leave one wave per SIMD: 58.6 us)
+        if constexpr (sizeof(T) == 4) {   // (four samples per workgroup halve the L2 stream but leave one wave per SIMD: 58.6 us)
           rc = od_kloop_launch<T, 2, 3, 2>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
           if (rc == MV_ERR_UNSUPPORTED) rc = od_kloop_launch<T, 1, 3, 2>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
         } else {
@@ -2127,59 +1939,45 @@ static int od_dispatch(const void* x, const void* packed, const void* bias, cons
         }
       }
       // two samples per workgroup share the staged weights, but a grid that leaves CUs idle loses more: input_proj at B = 32 is
-      // 1 x 8 x 16 = 128 workgroups with S = 2 - one sample per workgroup fills the chip (17.7 -> ~14 us; MV_OD_S1=0: never)
-      static int s1 = -1;
-      if (s1 < 0) { const char* e = getenv("MV_OD_S1"); s1 = e ? atoi(e) : 1; }
-      if (rc == MV_ERR_UNSUPPORTED && s1 && (long)cdiv(B, 2) * cdiv(p.M, 64) * cdiv(ntiles, 3) < 256) OD_GO(1, 1, 3);
+      // 1 x 8 x 16 = 128 workgroups with S = 2 - one sample per workgroup fills the chip (17.7 -> ~14 us)
+      if (rc == MV_ERR_UNSUPPORTED && (long)cdiv(B, 2) * cdiv(p.M, 64) * cdiv(ntiles, 3) < 256) OD_GO(1, 1, 3);
       if (rc == MV_ERR_UNSUPPORTED) OD_GO(2, 1, 3);
       if (rc == MV_ERR_UNSUPPORTED) OD_GO(1, 1, 3);
     } else if (wbytes > (1 << 20)) {         // big kernels, medium sequences: 144-column blocks amortise the aggregation
       rc = MV_ERR_UNSUPPORTED;
-      {
-        static int mt1 = -1;
-        if (mt1 < 0) { const char* e = getenv("MV_OD_MT1"); mt1 = e ? atoi(e) : 1; }
-        // 256 input channels, ks = 2*stride (ups1): 64-row workgroups keep their 16 mixed fragments per wave resident and walk
-        // the sample's 96-column tiles - the bank fragments are fetched from L2 and mixed once per (sample, row block) instead
-        // of once per tile (37 -> 28.5 us; 144-column tiles without the x look-ahead measured 34 us)
-        static int smp = -1;
-        if (smp < 0) { const char* e = getenv("MV_OD_SAMPLE"); smp = e ? atoi(e) : 1; }
-        // the whole sample resident in LDS, the mixed fragments streamed (ups1 at B = 32: see odconv_sample_kernel)
-        if (smp && transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && Cin == 256 && B * (p.M / 128) >= 128) {
-          if constexpr (sizeof(T) == 2) rc = od_sample_launch<T, 256, 17>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-        }
-        if (rc == MV_ERR_UNSUPPORTED && mt1 && transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && Cin == 256) {
-          // (fp32: 16 resident fragment PAIRS per wave need 256 VGPRs = one wave per SIMD: 98 us vs 77 on the one-tile kernel - not used)
-          if constexpr (sizeof(T) == 2) rc = od_mt_launch<T, 1, 6, 256>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-        }
+      // 256 input channels, ks = 2*stride (ups1): 64-row workgroups keep their 16 mixed fragments per wave resident and walk
+      // the sample's 96-column tiles - the bank fragments are fetched from L2 and mixed once per (sample, row block) instead
+      // of once per tile (37 -> 28.5 us; 144-column tiles without the x look-ahead measured 34 us)
+      // the whole sample resident in LDS, the mixed fragments streamed (ups1 at B = 32: see odconv_sample_kernel)
+      if (transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && Cin == 256 && B * (p.M / 128) >= 128) {
+        if constexpr (sizeof(T) == 2) rc = od_sample_launch<T, 256, 17>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+      }
+      if (rc == MV_ERR_UNSUPPORTED && transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && Cin == 256) {
+        // (fp32: 16 resident fragment PAIRS per wave need 256 VGPRs = one wave per SIMD: 98 us vs 77 on the one-tile kernel - not used)
+        if constexpr (sizeof(T) == 2) rc = od_mt_launch<T, 1, 6, 256>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
       }
       if (rc == MV_ERR_UNSUPPORTED) OD_GO(1, 2, 9);      // (fp32: 64- / 96-column tiles measured 96 / 94 us vs 76)
       if (rc == MV_ERR_UNSUPPORTED) OD_GO(1, 1, 3);
     } else {                                 // small kernels, long sequences: HBM-streaming regime
       rc = MV_ERR_UNSUPPORTED;
-      {
-        static int mt_on = -1;
-        if (mt_on < 0) { const char* e = getenv("MV_OD_MT"); mt_on = e ? atoi(e) : 1; }
-        if (mt_on && transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && (Cin == 64 || Cin == 128)) {
-          // 128-column tiles for 64 input channels; 64-column tiles for 128 (8 resident A fragments per M-tile: the wider tile
-          // would need > 256 VGPRs, i.e. one wave per SIMD - measured 42 vs 24.5 us)
-          if constexpr (sizeof(T) == 2) {
-            if (Cin == 64) rc = od_mt_launch<T, 2, 8, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-            else rc = od_mt_launch<T, 2, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-          } else {   // fp32 (operands are hi/lo register pairs): 64-column tiles; at 128 channels ONE M-tile per wave (two cost a wave per SIMD: 60 us)
-            static int os_on = -1;
-            if (os_on < 0) { const char* e = getenv("MV_OD_STREAM"); os_on = e ? atoi(e) : 1; }
-            if (os_on && act <= ACT_LRELU) {    // streaming form: 256-byte input rows (64 fp32 / 128 fp16 channels)
-              if (p.in_f16 && Cin == 128) rc = od_stream_launch<128, 4, true>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-              else if (!p.in_f16 && Cin == 64) rc = od_stream_launch<64, 8, false>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-            }
-            if (rc != MV_ERR_UNSUPPORTED) { /* launched (or sized) */ }
-            else if (p.out_pair) return rc;
-            else if (p.in_f16) {
-              if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-              else rc = od_mt_launch<T, 1, 4, 128, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-            } else if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-            else rc = od_mt_launch<T, 1, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);   // ups2 49 -> 38 us
+      if (transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && (Cin == 64 || Cin == 128)) {
+        // 128-column tiles for 64 input channels; 64-column tiles for 128 (8 resident A fragments per M-tile: the wider tile
+        // would need > 256 VGPRs, i.e. one wave per SIMD - measured 42 vs 24.5 us)
+        if constexpr (sizeof(T) == 2) {
+          if (Cin == 64) rc = od_mt_launch<T, 2, 8, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+          else rc = od_mt_launch<T, 2, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+        } else {   // fp32 (operands are hi/lo register pairs): 64-column tiles; at 128 channels ONE M-tile per wave (two cost a wave per SIMD: 60 us)
+          if (act <= ACT_LRELU) {    // streaming form: 256-byte input rows (64 fp32 / 128 fp16 channels)
+            if (p.in_f16 && Cin == 128) rc = od_stream_launch<128, 4, true>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+            else if (!p.in_f16 && Cin == 64) rc = od_stream_launch<64, 8, false>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
           }
+          if (rc != MV_ERR_UNSUPPORTED) { /* launched (or sized) */ }
+          else if (p.out_pair) return rc;
+          else if (p.in_f16) {
+            if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+            else rc = od_mt_launch<T, 1, 4, 128, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+          } else if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+          else rc = od_mt_launch<T, 1, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);   // ups2 49 -> 38 us
         }
       }
       if (p.in_f16 || p.out_pair) return rc;                 // only the multi-tile / streaming kernels widen their input / write pair rows

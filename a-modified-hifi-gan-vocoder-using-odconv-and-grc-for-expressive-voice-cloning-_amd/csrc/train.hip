@@ -535,12 +535,8 @@ extern "C" int mv_mel_loss(const void* wave, const float* fb, const float* targe
   MV_CHECK_ARG(kind == 0 || kind == 1);
   MV_CHECK_ARG((n_fft - hop) / 2 < T_);
   const int n_frames = T_ / hop, nb = n_fft / 2 + 1;
-  int logn = 0;                                       // rFFT path for power-of-two n_fft (env MV_MEL_DFT=1: the direct DFT, for comparison)
-  {
-    static int force_dft = -1;
-    if (force_dft < 0) { const char* e = getenv("MV_MEL_DFT"); force_dft = e ? atoi(e) : 0; }
-    if (!force_dft && n_fft >= 32 && (n_fft & (n_fft - 1)) == 0) while ((1 << logn) < n_fft) ++logn;
-  }
+  int logn = 0;                                       // rFFT path for power-of-two n_fft, the direct DFT otherwise
+  if (n_fft >= 32 && (n_fft & (n_fft - 1)) == 0) while ((1 << logn) < n_fft) ++logn;
   const size_t lds = sizeof(float) * ((logn > 0 ? 6 * (size_t)n_fft + nb : 3 * (size_t)n_fft + 3 * (size_t)nb) + n_mels + 32);
   if (lds > 160 * 1024 || B > 65535) return MV_ERR_UNSUPPORTED;
   const long n_total = (long)B * n_mels * n_frames;

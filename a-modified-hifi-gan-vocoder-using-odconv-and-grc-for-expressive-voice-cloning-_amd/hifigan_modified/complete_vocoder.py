@@ -314,14 +314,11 @@ class VocoderTrainer:
             if rng is not None:
                 rng.upload()
             st["graph"].replay()
-        if os.environ.get("MV_GRAPH_REPLAY_STREAM", "own") == "own":
-            cur = torch.cuda.current_stream()
-            gs.wait_stream(cur)
-            with torch.cuda.stream(gs):
-                replay()
-            cur.wait_stream(gs)
-        else:
+        cur = torch.cuda.current_stream()
+        gs.wait_stream(cur)
+        with torch.cuda.stream(gs):
             replay()
+        cur.wait_stream(gs)
         dopt.after_replay(st["dstate"])
         gopt.after_replay(st["gstate"])
         if rng is not None:

@@ -19,8 +19,6 @@ Deviations from the reference, on purpose:
 """
 from __future__ import annotations
 
-import os
-
 from typing import Optional, Tuple
 
 import torch
@@ -33,7 +31,7 @@ _RELU = (N.ACT_LRELU, 0.0)
 _NONE = (N.ACT_NONE, 0.0)
 _TANH = (N.ACT_TANH, 0.0)
 _UNFUSED_RES2 = False   # tests: force the conv-by-conv Res2Net chain
-_SKINNY_ROWS = int(__import__("os").environ.get("MV_SKINNY_ROWS", "4096"))     # up to this many positions the split-K GEMM beats the tiled conv kernel (tools/bench_embed.py)
+_SKINNY_ROWS = 4096     # up to this many positions the split-K GEMM beats the tiled conv kernel (tools/bench_embed.py)
 
 
 def _sig(mod: nn.Module):
@@ -371,7 +369,7 @@ class Emotion2Vec(nn.Module):
         return frame, utt, None
 
 
-_TWO_STREAMS = os.environ.get("MV_EMBED_STREAMS", "2") != "1"
+_TWO_STREAMS = True   # tests: False keeps both encoders on one stream
 _SIDE = {}
 
 
@@ -399,7 +397,7 @@ class EmbeddingExtractor(nn.Module):
             return self.speaker_extractor.embed(mel_spectrogram), self.emotion_extractor.embed(mel_spectrogram)
         # The two encoders are independent chains of ~40 short, latency-bound launches each: the emotion encoder runs on a second HIP
         # stream (fork / join by events - also what a graph capture records, so the replayed graph has two parallel branches) and the
-        # GPU overlaps them (0.53 -> ~0.3 ms per B = 32 x 32-frame batch).  MV_EMBED_STREAMS=1 keeps everything on one stream.
+        # GPU overlaps them (0.53 -> ~0.3 ms per B = 32 x 32-frame batch).
         main = torch.cuda.current_stream(mel_spectrogram.device)
         side = _side_stream(mel_spectrogram.device)
         side.wait_stream(main)

@@ -29,4 +29,4 @@ for T in (8192, 4096, 2048):
         fl = 2.0 * B * T * cin * cout * 15
         tot += us
         print(f"{kind:5s} T={T:5d} {cin:3d}->{cout:3d} {us:8.1f} us {fl / us / 1e6:7.1f} TF  err {err:.2e}", flush=True)
-print(f"total {tot/1e3:.2f} ms  M4={os.environ.get('MV_DCONV_M4')}")
+print(f"total {tot/1e3:.2f} ms")

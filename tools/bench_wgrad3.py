@@ -1,4 +1,4 @@
-"""3x3 weight-gradient kernel: parity against torch autograd and timing (MV_WGRAD3 = 0 / 1 per process)."""
+"""3x3 weight-gradient kernel: parity against torch autograd and timing."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,4 +37,4 @@ for P in (2, 7, 11):
         fl = 2.0 * B * Hh * W * cin * cout * 9
         tot += us
         print(f"wgrad P={P:2d} {cin:3d}->{cout:3d} {us:8.1f} us {fl / us / 1e6:7.1f} TF", flush=True)
-print(f"total {tot/1e3:.2f} ms  WGRAD3={os.environ.get('MV_WGRAD3')}")
+print(f"total {tot/1e3:.2f} ms")

@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: mel-frames/s vocoded by the V1 + ODConv + GRC-LoRA generator (BASELINE.json
 configs[1]: B=32 clips x 32 mel frames -> 8192 samples, 80-mel, 22.05 kHz, inference), one process per
-GPU.  Prints ONE JSON line on rank 0 (contract in the task description).
+GPU.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16|fp16] [--no-cpu-baseline] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype mixed|fp32|bf16|fp16] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes `--dump-outputs` and prints the
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the headline's configuration).  `--full` adds
+everything else, after the headline has been timed: the parity check against the CPU oracle, `cpu_baseline`, `roofline` /
+`roofline_odconv`, the other storage modes (`modes`, `bf16_storage`), `config_48k`, `config_v3_plain`, `conditioning` and the
+training metric `train`; the `--no-*` and `--train-*` options select among those legs and have no effect without `--full`.
 
 `--dump-outputs DIR` writes the waveform batch of the last timed step (rank 0; float32, [B, 1, 256 * frames]) to DIR/wave.npy.
 Weights and inputs are seeded, so the same arguments give the same inputs on every run and two builds can be compared on it.
@@ -16,7 +22,7 @@ rounding the 16-bit pipeline performs) shows that no pipeline with single 16-bit
 network: fp16 everywhere lands at 1.5e-3 (22 kHz) / 4.8e-3 (48 kHz) from rounding alone, bf16 at 1.2e-2.  The headline
 therefore runs the fastest mode that does meet it: fp32 storage with every MFMA operand split into a hi and a lo bf16
 part (three products per MAC, fp32 accumulate; `--dtype fp32`).  The 16-bit storage modes are timed beside it under
-"modes", each with its measured parity and `"parity_ok": false`.
+"modes" (`--full`), each with its measured parity and `"parity_ok": false`.
 
 A "step" is one generator forward over one batch of synthetic mels already resident in HBM.
 Inference shards by minibatch with no data-path collective (replicas only -> weak scaling).
@@ -248,6 +254,9 @@ def main():
                          "the second upsampler, fp32 behind it (both within north_star's 1e-3 on this configuration)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle parity check, the CPU baseline, the rooflines, the other storage modes, "
+                         "the 48 kHz / plain V3 / conditioning legs and the training metric (the options below select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-modes", action="store_true", help="skip the bf16 / fp16 storage legs")
     ap.add_argument("--no-conditioning", action="store_true", help="skip the embedding-extractor leg")
@@ -313,10 +322,10 @@ def main():
     # the MRF blocks of the mixed mode are the fp32-storage chain, with two-product operands in its streaming form (mrf_stream.hip)
     mrf_tag = ("fp32w16" if MIXED_MRF_W16 else "fp32") if args.dtype == "mixed" else args.dtype
 
-    # waveforms of 2 clips of this very configuration, checked against the oracle in the CPU leg (cpu_baseline)
+    # waveforms of 2 clips of this very configuration, checked against the oracle in the CPU leg (cpu_baseline, --full)
     checks = {}
     host = lambda t: t.float().cpu()
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad():
             checks["headline"] = (host(gen(mel[:2], spk[:2], emo[:2])), (host(mel[:2]), host(spk[:2]), host(emo[:2])))
 
@@ -360,6 +369,33 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0:
+        frames = B * Tm * world * args.steps
+        precision = {"mixed": "fp16 storage and MFMA operands through %s (prologue, input_proj + FiLM, the first upsamplers), then fp32 storage: the "
+                              "last upsamplers and the output conv with every MFMA operand split into hi + lo bf16 (3 products per MAC), the three MRF "
+                              "blocks with hi + lo f16 activation operands x %s; fp32 accumulate throughout"
+                              % (MIXED_THROUGH, "single f16 weights (2 products per MAC)" if MIXED_MRF_W16 else "hi + lo bf16 weights (3 products)"),
+                     "fp32": "fp32 storage; every MFMA operand split into hi + lo bf16 (3 products per MAC), fp32 accumulate",
+                     "bf16": "bf16 storage and MFMA operands, fp32 accumulate", "fp16": "fp16 storage and MFMA operands, fp32 accumulate"}[args.dtype]
+        out = {
+            "metric": "mel-frames/s vocoded (V1 80-mel 22.05kHz generator, ODConv + GRC-LoRA" + ("; mixed fp16 + fp32 storage: the fastest "
+                      "mode inside north_star's 1e-3 - BASELINE's bf16 storage is reported under bf16_storage with parity_ok false)" if args.dtype == "mixed" else ")"),
+            "value": round(frames / elapsed, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "fp16+fp32" if args.dtype == "mixed" else args.dtype, "precision": precision, "data": "synthetic",
+            "config": {"workload": "configs[1]: V1 generator + ODConv1d + GRC-LoRA, B=%d x %d mel frames -> %d samples, inference"
+                                   % (B, Tm, Tm * 256), "batch_per_gpu": B, "mel_frames": Tm, "n_mels": 80,
+                       "parallelism": "replicas (batch-sharded, no collective)"},
+            "samples_per_s": round(frames * 256 / elapsed, 1),
+            "launch": "eager" if args.eager else "hipgraph",
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # live roofline of the MRF ("ResBlock") stage: HIP events on the launch stream (torch's current stream) around
     # the fused channels-last block = 3 launches of mv::mrf_kernel<T,...,PASS=1|2|3> (GN5 stats, GN8 stats, output)
@@ -709,25 +745,8 @@ def main():
                                  "traffic": ttr["bytes"] if ttr else None, "flops_per_launch": flops, "ms_per_launch": round(ms, 4)}
 
     if rank == 0:
-        frames = B * Tm * world * args.steps
-        precision = {"mixed": "fp16 storage and MFMA operands through %s (prologue, input_proj + FiLM, the first upsamplers), then fp32 storage: the "
-                              "last upsamplers and the output conv with every MFMA operand split into hi + lo bf16 (3 products per MAC), the three MRF "
-                              "blocks with hi + lo f16 activation operands x %s; fp32 accumulate throughout"
-                              % (MIXED_THROUGH, "single f16 weights (2 products per MAC)" if MIXED_MRF_W16 else "hi + lo bf16 weights (3 products)"),
-                     "fp32": "fp32 storage; every MFMA operand split into hi + lo bf16 (3 products per MAC), fp32 accumulate",
-                     "bf16": "bf16 storage and MFMA operands, fp32 accumulate", "fp16": "fp16 storage and MFMA operands, fp32 accumulate"}[args.dtype]
-        out = {
-            "metric": "mel-frames/s vocoded (V1 80-mel 22.05kHz generator, ODConv + GRC-LoRA" + ("; mixed fp16 + fp32 storage: the fastest "
-                      "mode inside north_star's 1e-3 - BASELINE's bf16 storage is reported under bf16_storage with parity_ok false)" if args.dtype == "mixed" else ")"),
-            "value": round(frames / elapsed, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "fp16+fp32" if args.dtype == "mixed" else args.dtype, "precision": precision, "data": "synthetic",
-            "config": {"workload": "configs[1]: V1 generator + ODConv1d + GRC-LoRA, B=%d x %d mel frames -> %d samples, inference"
-                                   % (B, Tm, Tm * 256), "batch_per_gpu": B, "mel_frames": Tm, "n_mels": 80,
-                       "parallelism": "replicas (batch-sharded, no collective)"},
-            "samples_per_s": round(frames * 256 / elapsed, 1),
+        out.update({
             "parity_rel_l2_vs_oracle": None, "parity_tol": PARITY_TOL, "parity_ok": None,
-            "launch": "eager" if args.eager else "hipgraph",
             "roofline": roof,
             "roofline_odconv": od_roof,
             "modes": modes,
@@ -735,7 +754,7 @@ def main():
             "conditioning": conditioning,
             "config_48k": cfg48,
             "config_v3_plain": cfg_v3,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(sd_cpu, max(1, (os.cpu_count() or 2) // 2), checks=checks, embed_check=embed_check,
                               check48=checks48, check_v3=check_v3)

@@ -7,7 +7,7 @@ ROOTD=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOTD/gpurun_out/${TAG}_pipes
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--dtype fp32 --no-cpu-baseline --train-steps 0 --no-conditioning --no-v3 --no-48k --no-modes --steps 20 --warmup 3"
+ARGS="--full --dtype fp32 --no-cpu-baseline --train-steps 0 --no-conditioning --no-v3 --no-48k --no-modes --steps 20 --warmup 3"
 i=0
 for grp in "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_LDS" "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_ACTIVE_INST_VMEM"; do
   i=$((i+1)); d=$OUT/g$i; mkdir -p $d

@@ -9,10 +9,10 @@ ROOTD=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOTD/gpurun_out/${TAG}_prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-INF="--no-cpu-baseline --train-steps 0 --no-conditioning --no-v3 --no-48k --no-modes --steps 40 --warmup 5"
+INF="--full --no-cpu-baseline --train-steps 0 --no-conditioning --no-v3 --no-48k --no-modes --steps 40 --warmup 5"
 run() { d=$OUT/$1; shift; mkdir -p $d; "$@" > $d/log.txt 2>&1 || { tail -n 5 $d/log.txt; exit 1; }; echo "done $d"; }
-# 1. kernel-trace of the DEFAULT bench run (headline + modes + train + conditioning + 48k + plain V3)
-run bench_trace rocprofv3 --kernel-trace --output-format csv -d $OUT/bench_trace -- python3 $ROOTD/bench.py --steps 100
+# 1. kernel-trace of the --full bench run (headline + modes + train + conditioning + 48k + plain V3)
+run bench_trace rocprofv3 --kernel-trace --output-format csv -d $OUT/bench_trace -- python3 $ROOTD/bench.py --full --steps 100
 grep '^{"metric"' $OUT/bench_trace/log.txt > $OUT/bench_line_profiled.json || true
 # 2. HBM traffic, inference, per storage type: FETCH_SIZE and WRITE_SIZE in separate passes
 # (mixed = the headline mode: fp16 storage through up1, fp32 storage behind it, MRF chain with two-product operands - summary tag fp32w16)
@@ -21,7 +21,7 @@ for dt in mixed bf16; do
   run write_$dt rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write_$dt -- python3 $ROOTD/bench.py --dtype $dt $INF
 done
 # 3. HBM traffic, training step
-TR="--no-cpu-baseline --train-steps 2 --train-warmup 1 --no-conditioning --no-v3 --no-48k --no-modes --steps 5 --warmup 1"
+TR="--full --no-cpu-baseline --train-steps 2 --train-warmup 1 --no-conditioning --no-v3 --no-48k --no-modes --steps 5 --warmup 1"
 run fetch_train rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch_train -- python3 $ROOTD/bench.py $TR
 run write_train rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write_train -- python3 $ROOTD/bench.py $TR
 # 4. summaries (small; the raw csv files stay in gpurun_out/)

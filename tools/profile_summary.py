@@ -6,7 +6,7 @@
       from the trace so that it does not depend on the profiler version's own stats file.
 
   HBM traffic:    python tools/profile_summary.py traffic <FETCH_SIZE dir> <WRITE_SIZE dir> profiles/rNN_<dtype>_pmc_traffic.json \
-                         --dtype fp32 --workload "bench.py --dtype fp32 --train-steps 0 ..."
+                         --dtype fp32 --workload "bench.py --full --dtype fp32 --train-steps 0 ..."
       The two directories come from two SEPARATE passes (`rocprofv3 --pmc FETCH_SIZE --kernel-trace` and `--pmc WRITE_SIZE
       --kernel-trace`; gfx950 cannot count both at once, and counter passes must not be mixed with the trace domains gpurun
       refuses).  Units and the gfx950 correction follow MI355X_MICROARCH.md, section HBM: both counters are in KiB per

@@ -31,6 +31,7 @@ struct DcP {
 };
 
 // packed[mt][kstep][lane][8]: row o = 16*mt + lane&15, k-chunk = 4*kstep + lane>>4 -> tap = chunk / (Cin/8), c = 8*(chunk % (Cin/8)) + j
+// fp32 (split operands): every 2 KB fragment is the hi bf16 image followed by the lo image (Mma<float>::load_a(p, FRAG_BYTES))
 // flip == 0: forward weights  w[o][c][ih][iw]  (tap = ih*kw + iw)
 // flip == 1: data-gradient weights: rows = c (previous-layer channels), k runs over (flipped tap, o)
 template <typename T, typename P>
@@ -49,7 +50,8 @@ __global__ __launch_bounds__(256) void dconv_pack_kernel(const P* __restrict__ w
     float v = 0.f;
     if (!flip) { if (row < Cout && c < Cin) v = ld<P>(w + ((long)row * Cin + c) * taps + tap); }
     else if (c < Cout && row < Cin) v = ld<P>(w + ((long)c * Cin + row) * taps + (taps - 1 - tap));   // w[o=c][cin=row][flipped tap]
-    st<T>(out + idx, v);
+    if constexpr (Mma<T>::NSETS == 2) PackW<T>::put(reinterpret_cast<char*>(out) + fr * 2 * FRAG_BYTES, FRAG_BYTES, lane, j, v);
+    else st<T>(out + idx, v);
   }
 }
 
@@ -68,7 +70,9 @@ __global__ __launch_bounds__(256) void dconv_multi_pack_kernel(const MultiPackDe
     const int row = 16 * mt + (lane & 15), chunk = 4 * kstep + (lane >> 4);
     const int tap = chunk / cpc, c = 8 * (chunk % cpc) + j;
     const float v = !d.flip ? d.src[((long)row * d.Cin + c) * taps + tap] : d.src[((long)c * d.Cin + row) * taps + (taps - 1 - tap)];
-    if (d.dtype == MV_BF16) st<bf16>((bf16*)d.dst + idx, v); else st<f16>((f16*)d.dst + idx, v);
+    if (d.dtype == MV_F32) PackW<float>::put(reinterpret_cast<char*>(d.dst) + fr * 2 * FRAG_BYTES, FRAG_BYTES, lane, j, v);
+    else if (d.dtype == MV_BF16) st<bf16>((bf16*)d.dst + idx, v);
+    else st<f16>((f16*)d.dst + idx, v);
   }
 }
 
@@ -271,9 +275,13 @@ __global__ __launch_bounds__(NWV * 64, 2) void dconv_cl_wide_kernel(const T* __r
   using M = Mma<T>;
   using V = typename M::V;
   constexpr int ES = M::ES, RG = NWV / PS, NPOS = PS * NB * 16, NT = NWV * 64;   // PS position slices x RG row groups = NWV waves; CCH channels staged at a time
+  // NS = 2 (fp32): the tile is staged as pre-split hi and lo bf16 planes (split once per staged element, not once per read) and
+  // every weight fragment is a hi + a lo image; 16-bit storage has one plane and one image
+  constexpr int NS = M::NSETS, FB = FRAG_BYTES * NS;
   extern __shared__ __align__(16) char lds[];
-  const int RS = lds_row_stride(CCH * ES, ES);
+  const int RS = lds_row_stride(CCH * 2, 2);             // one 16-bit plane row
   const int prow = NPOS + (p.kw - 1) * p.dil;
+  const int PL = NS == 2 ? p.kh * prow * RS : 0;         // byte offset of the lo plane
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 15, g = lane >> 4;
   const int ps = wid / RG, rg = wid % RG;                // position slice, row group
@@ -301,13 +309,22 @@ __global__ __launch_bounds__(NWV * 64, 2) void dconv_cl_wide_kernel(const T* __r
         while (r >= prow) { r -= prow; ++pl; }
         const int hh = h - ph + pl, ww = w0 - pw + r;
         v[u] = u32x4{0u, 0u, 0u, 0u};
-        dsto[u] = R < nrow ? R * RS + ch * 16 : -1;
+        dsto[u] = R < nrow ? R * RS + ch * (16 / NS) : -1;
         if (R < nrow && hh >= 0 && hh < p.H && ww >= 0 && ww < p.W)
           v[u] = *reinterpret_cast<const u32x4*>(xb + ((long)hh * p.W + ww) * p.Cin * ES);
       }
 #pragma unroll
       for (int u = 0; u < UB; ++u)
-        if (dsto[u] >= 0) *reinterpret_cast<u32x4*>(lds + dsto[u]) = v[u];
+        if (dsto[u] >= 0) {
+          if constexpr (NS == 2) {                        // 4 fp32 channels -> 8 bytes of the hi plane + 8 bytes of the lo plane
+            u32x2 hi, lo;
+            M::split4(__builtin_bit_cast(f32x4, v[u]), hi, lo);
+            *reinterpret_cast<u32x2*>(lds + dsto[u]) = hi;
+            *reinterpret_cast<u32x2*>(lds + PL + dsto[u]) = lo;
+          } else {
+            *reinterpret_cast<u32x4*>(lds + dsto[u]) = v[u];
+          }
+        }
     }
   };
 
@@ -323,7 +340,8 @@ __global__ __launch_bounds__(NWV * 64, 2) void dconv_cl_wide_kernel(const T* __r
 #pragma unroll
     for (int mw = 0; mw < MW; ++mw) {
       const int mt = (mt0 + mw) < n_mt ? (mt0 + mw) : (n_mt - 1);
-      dst[mw] = M::load_b(wlane + ((long)mt * p.ksteps + kid) * 1024);
+      if constexpr (NS == 2) dst[mw] = M::load_a(wlane + ((long)mt * p.ksteps + kid) * FB, FRAG_BYTES);
+      else dst[mw] = M::load_b(wlane + ((long)mt * p.ksteps + kid) * 1024);
     }
   };
   // k-steps in execution order: chunk-major, then tap, then the 4 channel blocks of the chunk
@@ -345,13 +363,16 @@ __global__ __launch_bounds__(NWV * 64, 2) void dconv_cl_wide_kernel(const T* __r
     __syncthreads();
     for (int tap = 0; tap < taps; ++tap) {
       const int ih = tap / p.kw, iw = tap - ih * p.kw;
-      const char* brow = lds + ((long)ih * prow + iw * p.dil + ps * NB * 16 + col) * RS + 8 * g * ES;
+      const char* brow = lds + ((long)ih * prow + iw * p.dil + ps * NB * 16 + col) * RS + 8 * g * 2;
 #pragma unroll
       for (int j = 0; j < cc32; ++j) {
         fetch_next(a2);
         V bf[NB];
 #pragma unroll
-        for (int n = 0; n < NB; ++n) bf[n] = M::load_b(brow + j * 32 * ES + (long)(n * 16) * RS);
+        for (int n = 0; n < NB; ++n) {
+          if constexpr (NS == 2) bf[n] = M::load_bp(brow + j * 64 + (long)(n * 16) * RS, PL);
+          else bf[n] = M::load_b(brow + j * 32 * ES + (long)(n * 16) * RS);
+        }
         // all NB operand reads in flight before the first MFMA: left alone, the scheduler issues them two at a time, each pair
         // right in front of the 2 x MW MFMAs that use it (rr wait MMMM wait MMMM rr ...), one LDS round trip per 8 MFMAs
         __builtin_amdgcn_sched_barrier(0);
@@ -743,20 +764,23 @@ __global__ __launch_bounds__(512) void dconv_wgrad_kernel(const T* __restrict__ 
                                                           int xW, long sample_stride) {
   // xW: rows per image line of x (= W, or W + 1 for the even-tap ODConv adjoint whose x operand is one row longer);
   // sample_stride > 0: per-sample tiles - a workgroup's chunks all belong to sample (first chunk) / (H * wsplit)
-  static_assert(sizeof(T) == 2, "MFMA weight gradient needs 16-bit storage");
+  // fp32 storage (NS = 2): both operands are staged as pre-split hi and lo bf16 planes (the transposed reads work on 16-bit
+  // planes) and every product is Mma<float>'s three bf16 MFMAs with fp32 accumulation
   using M = Mma<T>;
   typedef __attribute__((ext_vector_type(4))) short s16x4;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
+  constexpr int ES = M::ES, NS = M::NSETS, LPPR = ES == 4 ? 4 : 3, PPR = 1 << LPPR, EP = 16 / ES;   // 16-byte pieces per 64-channel row, elements per piece
   constexpr int TAPS = TAPS_H * TAPS_W, TPW = (TAPS + 1) / 2;
   constexpr int PH = TAPS_H / 2;
   constexpr int RS = 160;                                   // 64 channels x 2 bytes + 32: conflict-free transposed reads
   constexpr int GROWS = WT;
   constexpr int MAXHALO = TAPS_H == 1 ? 64 : TAPS_W - 1;    // (TAPS_W - 1) * dil, checked by the launcher
-  constexpr int NLD = ((GROWS + TAPS_H * (WT + MAXHALO)) * 8 + 511) / 512;   // 16-byte pieces per thread per chunk
+  constexpr int NLD = ((GROWS + TAPS_H * (WT + MAXHALO)) * PPR + 511) / 512;   // 16-byte pieces per thread per chunk
   const int PW = (TAPS_W & 1) ? (TAPS_W / 2) * dil : 0;    // even tap counts: offsets 0 .. TAPS_W-1 (no centring)
   const int XCOLS = WT + (TAPS_W - 1) * dil;
   const int ROWS = GROWS + TAPS_H * XCOLS;
-  const int BUF = ROWS * RS;
+  const int PLW = ROWS * RS;                                // byte offset of the lo plane within a buffer
+  const int BUF = PLW * NS;
   extern __shared__ __align__(16) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -779,12 +803,20 @@ __global__ __launch_bounds__(512) void dconv_wgrad_kernel(const T* __restrict__ 
   }
   const int ga = (4 * grp + q) * RS + (wm * 32 + 4 * pp) * 2;
   const int xa = GROWS * RS + (4 * grp + q) * RS + (wn * 32 + 4 * pp) * 2;
-  auto trload = [&](const char* p0) {
+  auto trplane = [&](const char* p0) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)p0);
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p0 + 16 * RS));
     const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return both;
+  };
+  auto trload = [&](const char* p0) {
     typename M::V r;
-    r.v = __builtin_bit_cast(decltype(r.v), both);
+    if constexpr (NS == 2) {
+      r.hi = __builtin_bit_cast(bf16x8_t, trplane(p0));
+      r.lo = __builtin_bit_cast(bf16x8_t, trplane(p0 + PLW));
+    } else {
+      r.v = __builtin_bit_cast(decltype(r.v), trplane(p0));
+    }
     return r;
   };
 
@@ -796,17 +828,17 @@ __global__ __launch_bounds__(512) void dconv_wgrad_kernel(const T* __restrict__ 
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + i * 512;
-      const int r = idx >> 3, ch = idx & 7;
+      const int r = idx >> LPPR, ch = idx & (PPR - 1);
       pre[i] = u32x4{0u, 0u, 0u, 0u};
       if (r < GROWS) {
         const int ww = w0 + r;
-        if (ww < W && o0 + ch * 8 < Cout) pre[i] = *reinterpret_cast<const u32x4*>(g + (((long)b * H + h) * W + ww) * Cout + o0 + ch * 8);
+        if (ww < W && o0 + ch * EP < Cout) pre[i] = *reinterpret_cast<const u32x4*>(g + (((long)b * H + h) * W + ww) * Cout + o0 + ch * EP);
       } else if (r < ROWS) {
         const int rr = r - GROWS;
         const int pl = TAPS_H == 1 ? 0 : rr / XCOLS, col = rr - pl * XCOLS;
         const int hh = h - PH + pl, ww = w0 - PW + col;
-        if (hh >= 0 && hh < H && ww >= 0 && ww < xW && c0 + ch * 8 < Cin)
-          pre[i] = *reinterpret_cast<const u32x4*>(x + (((long)b * H + hh) * xW + ww) * Cin + c0 + ch * 8);
+        if (hh >= 0 && hh < H && ww >= 0 && ww < xW && c0 + ch * EP < Cin)
+          pre[i] = *reinterpret_cast<const u32x4*>(x + (((long)b * H + hh) * xW + ww) * Cin + c0 + ch * EP);
       }
     }
   };
@@ -814,7 +846,17 @@ __global__ __launch_bounds__(512) void dconv_wgrad_kernel(const T* __restrict__ 
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + i * 512;
-      if (idx < ROWS * 8) *reinterpret_cast<u32x4*>(lds + buf * BUF + (idx >> 3) * RS + (idx & 7) * 16) = pre[i];
+      if constexpr (NS == 2) {
+        if (idx < ROWS * PPR) {
+          char* dst = lds + buf * BUF + (idx >> LPPR) * RS + (idx & (PPR - 1)) * 8;
+          u32x2 hi, lo;
+          M::split4(__builtin_bit_cast(f32x4, pre[i]), hi, lo);
+          *reinterpret_cast<u32x2*>(dst) = hi;
+          *reinterpret_cast<u32x2*>(dst + PLW) = lo;
+        }
+      } else {
+        if (idx < ROWS * 8) *reinterpret_cast<u32x4*>(lds + buf * BUF + (idx >> 3) * RS + (idx & 7) * 16) = pre[i];
+      }
     }
   };
 
@@ -831,18 +873,28 @@ __global__ __launch_bounds__(512) void dconv_wgrad_kernel(const T* __restrict__ 
     if (more) issue(chunk + 1);
     const char* base = lds + buf * BUF;
     if (do_gb) {
-      const T* gcol = reinterpret_cast<const T*>(base) + (tid & 63);
+      if constexpr (NS == 2) {                              // hi + lo: the fp32 value to 2^-17
+        const char* gcol = base + (tid & 63) * 2;
 #pragma unroll
-      for (int i = 0; i < WT / 8; ++i)
-        bsum += ld<T>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(gcol) + ((tid >> 6) + 8 * i) * RS));
+        for (int i = 0; i < WT / 8; ++i) {
+          const int off = ((tid >> 6) + 8 * i) * RS;
+          bsum += ld<bf16>(reinterpret_cast<const bf16*>(gcol + off)) + ld<bf16>(reinterpret_cast<const bf16*>(gcol + PLW + off));
+        }
+      } else {
+        const T* gcol = reinterpret_cast<const T*>(base) + (tid & 63);
+#pragma unroll
+        for (int i = 0; i < WT / 8; ++i)
+          bsum += ld<T>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(gcol) + ((tid >> 6) + 8 * i) * RS));
+      }
     }
 #pragma unroll 1
     for (int k0 = 0; k0 < WT; k0 += 32) {
       typename M::V a[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m) a[m] = trload(base + ga + k0 * RS + m * 32);
-      // a batch of transposed B fragments first (independent LDS reads in flight), then their MFMAs
-      constexpr int BT = TPW > 5 ? 4 : TPW;
+      // a batch of transposed B fragments first (independent LDS reads in flight), then their MFMAs (fp32: two taps, the
+      // operands are twice as wide)
+      constexpr int BT = NS == 2 ? 2 : (TPW > 5 ? 4 : TPW);
 #pragma unroll
       for (int tb = 0; tb < TPW; tb += BT) {
         typename M::V bfr[BT][2];
@@ -1367,7 +1419,31 @@ static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias
   if (head_pf && (Cout != 256 || dtype == MV_F32 || act_save || B * H > 65535)) return MV_ERR_UNSUPPORTED;   // needs the 256-row workgroups
   DcP p{B, H, W, Cin, Cout, kh, kw, act, slope, kh * kw * (Cin / 32), Cin / 32, dil_w, Cin, head_pf, head_z, head_taps};
   int rc = MV_ERR_DTYPE;
-  if (dtype != MV_F32 && B * H <= 65535) {
+  if (dtype == MV_F32) {
+    // split-operand fp32 (Mma<float>, three bf16 products per MAC): 4 waves = 2 position slices x 2 row groups, 128 positions and
+    // 32 / 64 / 128 rows per workgroup.  The hi/lo planes cost 4 bytes per staged channel and position, twice the 16-bit tile, so
+    // the channel chunk is 32 for 3x3 (75 KB) and 64 for the one-row kernels (45 KB): two workgroups per CU either way
+    if (B * H > 65535) return MV_ERR_UNSUPPORTED;
+    const int cch = (kh == 1 && Cin % 64 == 0) ? 64 : 32;
+    const int rows = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
+    p.cchunk = cch;
+    const size_t xb = 2 * (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(cch * 2, 2);
+    const size_t ob = (size_t)128 * (rows * 4 + 16);
+    const size_t ldsb = xb > ob ? xb : ob;
+    if (ldsb > 160 * 1024) return MV_ERR_UNSUPPORTED;
+    dim3 grid(cdiv(W, 128), cdiv(Cout, rows), B * H);
+    hipStream_t st_ = (hipStream_t)stream;
+#define MV_F32W(MW_, CC_) do { auto kern = dconv_cl_wide_kernel<float, 2, MW_, 4, CC_, 4>; static size_t lds_set_f = 0; \
+      if (ldsb > lds_set_f) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); lds_set_f = ldsb; } \
+      hipLaunchKernelGGL(kern, grid, dim3(256), ldsb, st_, (const float*)x, (const float*)packed, (const float*)bias, (const float*)act_save, (float*)y, p); } while (0)
+#define MV_F32R(CC_) do { if (rows == 128) MV_F32W(4, CC_); else if (rows == 64) MV_F32W(2, CC_); else MV_F32W(1, CC_); } while (0)
+    if (cch == 64) MV_F32R(64); else MV_F32R(32);
+#undef MV_F32R
+#undef MV_F32W
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+  }
+  if (B * H <= 65535) {
     // 8-wave chunked variant: picked where it measured faster than the whole-Cin tile (tools/bench_dconv.py, B=32):
     // every wide input (Cin > 128), and narrow outputs of 3x3 layers, where the whole-Cin kernel leaves waves idle
     const size_t full = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(Cin * 2, 2);
@@ -1440,7 +1516,8 @@ static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias
     }
     p.cchunk = Cin;
   }
-  MV_DISPATCH(dtype, {
+  auto whole = [&](auto tag) {   // 16-bit storage only: fp32 returned above
+    using T = decltype(tag);
     hipStream_t s_ = (hipStream_t)stream;
     if (Cout >= 256) {        // 4 waves x 64 rows: one B fragment feeds 4 MFMAs (LDS reads per MFMA halved), two workgroups per CU
       rc = dconv_launch<T, 4, 4, 8>(x, packed, bias, act_save, y, p, s_);
@@ -1451,7 +1528,8 @@ static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias
       rc = dconv_launch<T, 4, 1, 8>(x, packed, bias, act_save, y, p, s_);
       if (rc == MV_ERR_UNSUPPORTED) rc = dconv_launch<T, 4, 1, 4>(x, packed, bias, act_save, y, p, s_);
     }
-  });
+  };
+  if (dtype == MV_BF16) whole(bf16{}); else if (dtype == MV_F16) whole(f16{}); else return MV_ERR_DTYPE;
   if (rc != MV_OK) return rc;
   MV_LAUNCH_CHECK();
   return MV_OK;
@@ -1613,6 +1691,38 @@ static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, i
   return MV_OK;
 }
 
+// fp32 split operands: the staged chunk is twice the 16-bit one (hi + lo planes), so it holds 64 positions of a k15 row or 32 of
+// a 3x3 row (91 / 86 KB for both buffers)
+template <int TH, int TW>
+static int dwgrad_f32_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, hipStream_t s) {
+  constexpr int WT = TH == 1 ? 64 : 32;
+  const int wsplit = cdiv(W, WT);
+  const size_t lds = 2 * 2 * (size_t)(WT + TH * (WT + TW - 1)) * 160;
+  auto kern = dconv_wgrad_kernel<float, TH, TW, WT>;
+  static bool lds_set = false;
+  if (!lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = true; }
+  const long nchunks = (long)B * H * wsplit;
+  if (nchunks > (1L << 30)) return MV_ERR_UNSUPPORTED;
+  const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
+  constexpr int target = 256;
+  int groups = target / tiles; if (groups < 1) groups = 1; if (groups > nchunks) groups = (int)nchunks;
+  const int cpw = (int)((nchunks + groups - 1) / groups);
+  groups = (int)((nchunks + cpw - 1) / cpw);
+  if (groups > 65535) return MV_ERR_UNSUPPORTED;
+  dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), groups);
+  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const float*)x, (const float*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw, 1,
+                     W, 0L);
+  return MV_OK;
+}
+
+static bool dwgrad_f32_ok(int kh, int kw, int dil) { return dil == 1 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 15)); }
+
+static int dwgrad_f32_dispatch(const void* x, const void* g, float* ws, float* gb, int B, int H, int W, int Cin, int Cout, int kh, int kw,
+                               hipStream_t s) {
+  if (kh == 3) return dwgrad_f32_launch<3, 3>(x, g, ws, gb, B, H, W, Cin, Cout, s);
+  return dwgrad_f32_launch<1, 15>(x, g, ws, gb, B, H, W, Cin, Cout, s);
+}
+
 template <typename T>
 static int dwgrad_dispatch(const void* x, const void* g, float* ws, float* gb, int B, int H, int W, int Cin, int Cout, int kh, int kw,
                            int dil, hipStream_t s) {
@@ -1635,7 +1745,7 @@ extern "C" int mv_dconv_wgrad_cl(const void* x, const void* g, float* gw, float*
                                  int Cout, int kh, int kw, int dil_w, int dtype, void* stream) {
   MV_CHECK_ARG(x && g && gw && workspace && B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0 && dil_w >= 1);
   MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0);
-  if (dtype == MV_F32) return MV_ERR_UNSUPPORTED;   // 16-bit storage only (transposed LDS reads); callers fall back to the generic kernel
+  if (dtype == MV_F32 && !dwgrad_f32_ok(kh, kw, dil_w)) return MV_ERR_UNSUPPORTED;   // fp32: the discriminator geometries only
   hipStream_t s = (hipStream_t)stream;
   const size_t wn = (size_t)Cout * Cin * kh * kw;
   if (gb && gb == workspace + wn) {                  // bias sums placed right behind the workspace: one fill instead of two
@@ -1647,6 +1757,7 @@ extern "C" int mv_dconv_wgrad_cl(const void* x, const void* g, float* gw, float*
   int rc = MV_ERR_UNSUPPORTED;
   if (dtype == MV_BF16) rc = dwgrad_dispatch<bf16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, s);
   else if (dtype == MV_F16) rc = dwgrad_dispatch<f16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, s);
+  else if (dtype == MV_F32) rc = dwgrad_f32_dispatch(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, s);
   if (rc != MV_OK) return rc;
   const long total = (long)Cout * Cin * kh * kw;
   hipLaunchKernelGGL(dconv_wgrad_reorder_kernel, dim3((unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256)), dim3(256),
@@ -1659,12 +1770,13 @@ extern "C" int mv_dconv_wgrad_cl_pz(const void* x, const void* g, float* gw, flo
                                     int Cout, int kh, int kw, int dil_w, int dtype, void* stream) {
   MV_CHECK_ARG(x && g && gw && workspace && B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0 && dil_w >= 1);
   MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0);
-  if (dtype == MV_F32) return MV_ERR_UNSUPPORTED;
+  if (dtype == MV_F32 && !dwgrad_f32_ok(kh, kw, dil_w)) return MV_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const long total = (long)Cout * Cin * kh * kw;
   int rc = MV_ERR_UNSUPPORTED;
   if (dtype == MV_BF16) rc = dwgrad_dispatch<bf16>(x, g, workspace, workspace + total, B, H, W, Cin, Cout, kh, kw, dil_w, s);
   else if (dtype == MV_F16) rc = dwgrad_dispatch<f16>(x, g, workspace, workspace + total, B, H, W, Cin, Cout, kh, kw, dil_w, s);
+  else if (dtype == MV_F32) rc = dwgrad_f32_dispatch(x, g, workspace, workspace + total, B, H, W, Cin, Cout, kh, kw, s);
   if (rc != MV_OK) return rc;
   hipLaunchKernelGGL(dconv_wgrad_finalize_kernel, dim3((unsigned)((total + Cout + 255) / 256 > 2048 ? 2048 : (total + Cout + 255) / 256)),
                      dim3(256), 0, s, workspace, gw, gb, Cout * Cin, kh * kw, Cout);

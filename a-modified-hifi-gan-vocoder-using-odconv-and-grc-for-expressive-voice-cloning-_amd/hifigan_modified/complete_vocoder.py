@@ -104,7 +104,11 @@ class VocoderTrainer:
     (functional.DropoutRNG, key from torch's CPU generator at construction): a captured step then draws fresh masks at every replay,
     the same ones the eager step would.  `"torch"` (the default otherwise) draws each mask's key from torch's CPU generator as
     before - under capture those keys are frozen into the graph.  `schedulers`: lr schedules (e.g. optim.WarmupCosineLR), stepped
-    after every train_step, eager or replayed.  The dropout stream and the schedules are saved in the checkpoint."""
+    after every train_step, eager or replayed.  The dropout stream and the schedules are saved in the checkpoint.
+
+    fp32 training with the discriminators on the matrix cores: `vocoder.discriminators.set_fp32_operands("split")` with fp32
+    activations runs both discriminator families on split-operand MFMA kernels (every operand hi + lo bf16, ~2^-16 relative) instead
+    of the generic fp32 kernels (the default "exact"); 16-bit activations are not affected."""
 
     def __init__(self, vocoder: ModifiedHiFiGANVocoder, generator_optimizer=None, discriminator_optimizer=None,
                  device=None, mel_mode: str = "stft", grad_sync=None, bucket_mib: int = 8, use_graph: bool = False,

@@ -1,10 +1,13 @@
-"""Channels-last MFMA path of one discriminator stack (forward + backward), 16-bit storage.
+"""Channels-last MFMA path of one discriminator stack (forward + backward): 16-bit storage, or fp32 storage in "split" mode.
 
 One ``torch.autograd.Function`` runs all five layers of a Discriminator2D / Discriminator1D
 (discriminators.py:56-66, :97-107): first layer (1 -> 32) and head (256 -> 1) as small dedicated kernels, the three
 wide layers on MFMA (``mv_dconv_cl_fwd``), their data gradients with the same kernel on flipped weights (LeakyReLU'
 fused in the epilogue) and their weight gradients with the transposed-LDS-read GEMM (``mv_dconv_wgrad_cl``).
-fp32 storage keeps using the generic kernels (functional.disc2d / disc1d).
+fp32 storage runs here only when the module's `fp32_operands` is "split" (discriminators.py): the wide layers then use the
+split-operand kernels (every operand hi + lo bf16, three products per MAC, fp32 accumulation, ~2^-16 relative); the first layer,
+the head's weight gradient and the first layer's gradients use their fp32 VALU kernels, and the head's forward and data gradient
+ride the wide conv zero-padded to 32 channels.  The default "exact" mode keeps the generic fp32 kernels (functional.disc2d / disc1d).
 """
 from __future__ import annotations
 
@@ -49,7 +52,7 @@ class _PackCache:
         ents = []
         for key, e in self.d.items():
             kind, p = key[1], e[0]()
-            if (p is None or not isinstance(kind, tuple) or len(kind) != 2 or kind[0] not in (torch.bfloat16, torch.float16)
+            if (p is None or not isinstance(kind, tuple) or len(kind) != 2 or kind[0] not in (torch.bfloat16, torch.float16, torch.float32)
                     or p.dtype != torch.float32 or not p.is_contiguous() or not opt.owns(p)):
                 continue
             w = _as4d(p)
@@ -151,7 +154,7 @@ class _DiscStack(Function):
         acts.append(a)
         C4 = ws[4].shape[1]
         hkh, hkw = ws[4].shape[2], ws[4].shape[3]
-        mfma_head = C4 == 256 and hkh * hkw <= 16
+        mfma_head = C4 == 256 and hkh * hkw <= 16 and dt != torch.float32     # fp32: the padded-conv head below
         zws, head_fused = None, False
         for li in (1, 2, 3):
             Cout, Cin = ws[li].shape[0], ws[li].shape[1]
@@ -206,7 +209,7 @@ class _DiscStack(Function):
         C4 = ws[4].shape[1]
         if need_w:
             taps = kh * kw
-            if taps <= 16 and C4 % 8 == 0:
+            if taps <= 16 and C4 % 8 == 0 and dt != torch.float32:
                 # gw[tap][c] = sum_pos G[pos][tap] x[pos][c] with G = the flipped tap matrix of gy: a 1x1 weight-gradient GEMM
                 # on the MFMA kernel; the centre column of G sums to the bias gradient
                 tm = torch.empty(B, H, W, 16, device=dev, dtype=dt)
@@ -221,7 +224,7 @@ class _DiscStack(Function):
             N.call("mv_ntc_to_nct", _P(gwt), _P(gw5), 1, C4, taps, N.MV_F32, st())
             grads[8], grads[9] = to(gw5, params[8]), to(gb5, params[9])
         g = torch.empty(B, H, W, C4, device=dev, dtype=dt)
-        if C4 == 256 and kh * kw <= 16:
+        if C4 == 256 and kh * kw <= 16 and dt != torch.float32:
             N.call("mv_dhead_dgrad", _P(gy), _P(_packs.head_mfma(params[8], dt)), _P(acts[3]), _P(g), B, H, W, C4, kh, kw, slope,
                    ops._dt(gy), st())
         else:
@@ -245,7 +248,7 @@ class _DiscStack(Function):
         C1 = ws[0].shape[0]
         if need_w:
             taps = kh * kw
-            if taps <= 16 and C1 % 8 == 0:
+            if taps <= 16 and C1 % 8 == 0 and dt != torch.float32:
                 # gw[o][tap] = sum_pos g1[pos][o] X[pos][tap] with X = the tap matrix of x0 (1x1 weight-gradient GEMM on MFMA)
                 tm = torch.empty(B, H, W, 16, device=dev, dtype=dt)
                 N.call("mv_tap_matrix", _P(x0), _P(tm), B, H, W, kh, kw, 0, ops._dt(g), st())
@@ -268,7 +271,10 @@ _cache = ops._ParamCache()
 
 
 def supported(x, blk) -> bool:
-    return x.dtype in (torch.bfloat16, torch.float16)
+    """16-bit storage always; fp32 storage when the stack's `fp32_operands` is "split" (on the GPU)."""
+    if x.dtype in (torch.bfloat16, torch.float16):
+        return True
+    return x.dtype == torch.float32 and x.is_cuda and getattr(blk, "fp32_operands", "exact") == "split"
 
 
 def disc_stack(x0, blk, slope=0.1):

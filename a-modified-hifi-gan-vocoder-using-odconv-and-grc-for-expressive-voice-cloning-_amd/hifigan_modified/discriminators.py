@@ -3,6 +3,10 @@
 Drop-in for the reference's ``hifigan_modified/discriminators.py``: MultiPeriodDiscriminator :12-28,
 MultiScaleDiscriminator :30-46, Discriminator2D :48-84 (zero right-pad + ``view(B,C,period,T//period)``
 fold, 5x Conv2d 3x3), Discriminator1D :86-117 (AvgPool1d + 5x Conv1d k15), HiFiGANDiscriminators :119-151.
+
+fp32 operands (fp32 storage only; host state like the generator's set_mixed_precision, no parameters or buffers):
+``"exact"`` (the default) runs the generic fp32 kernels; ``"split"`` runs the channels-last MFMA stack with every operand
+split into hi + lo bf16 and three products per MAC (disc_fused.py, ~2^-16 relative).
 """
 from __future__ import annotations
 
@@ -14,9 +18,28 @@ import torch.nn as nn
 from . import functional as Fn
 
 _CH = (1, 32, 64, 128, 256, 1)
+FP32_OPERAND_MODES = ("exact", "split")
 
 
-class Discriminator2D(nn.Module):
+class _Fp32Operands:
+    """`set_fp32_operands(mode)` / `fp32_operands` of every discriminator module: the mode is set on the module and on all the
+    discriminator modules inside it."""
+    _fp32_operands = "exact"
+
+    @property
+    def fp32_operands(self) -> str:
+        return self._fp32_operands
+
+    def set_fp32_operands(self, mode: str):
+        if mode not in FP32_OPERAND_MODES:
+            raise ValueError(f"fp32 operand mode must be one of {FP32_OPERAND_MODES}, got {mode!r}")
+        for m in self.modules():
+            if isinstance(m, _Fp32Operands):
+                m._fp32_operands = mode
+        return self
+
+
+class Discriminator2D(_Fp32Operands, nn.Module):
     def __init__(self, period: int):
         super().__init__()
         self.period = period
@@ -31,7 +54,7 @@ class Discriminator2D(nn.Module):
         return Fn.disc2d(x, self)
 
 
-class Discriminator1D(nn.Module):
+class Discriminator1D(_Fp32Operands, nn.Module):
     def __init__(self, scale: int):
         super().__init__()
         self.scale = scale
@@ -47,7 +70,7 @@ class Discriminator1D(nn.Module):
         return Fn.disc1d(x, self)
 
 
-class MultiPeriodDiscriminator(nn.Module):
+class MultiPeriodDiscriminator(_Fp32Operands, nn.Module):
     def __init__(self, periods: List[int] = [2, 3, 5, 7, 11]):
         super().__init__()
         self.periods = periods
@@ -57,7 +80,7 @@ class MultiPeriodDiscriminator(nn.Module):
         return [d(x) for d in self.discriminators]
 
 
-class MultiScaleDiscriminator(nn.Module):
+class MultiScaleDiscriminator(_Fp32Operands, nn.Module):
     def __init__(self, scales: List[int] = [1, 2, 4]):
         super().__init__()
         self.scales = scales
@@ -67,7 +90,7 @@ class MultiScaleDiscriminator(nn.Module):
         return [d(x) for d in self.discriminators]
 
 
-class HiFiGANDiscriminators(nn.Module):
+class HiFiGANDiscriminators(_Fp32Operands, nn.Module):
     def __init__(self):
         super().__init__()
         self.mpd = MultiPeriodDiscriminator()

@@ -785,7 +785,7 @@ def disc2d(x, blk):
     else:
         h = _t().OPS.mpd_fold(x, blk.period) if DISPATCH == "torch_ops" else _MpdFold.apply(x, blk.period)
     from . import disc_fused
-    if disc_fused.supported(x, blk):      # 16-bit storage: channels-last MFMA stack (csrc/disc_fused.hip)
+    if disc_fused.supported(x, blk):      # 16-bit storage or split fp32: channels-last MFMA stack (csrc/disc_fused.hip)
         return disc_fused.disc_stack(h, blk)
     for li, conv in enumerate(_convs(blk.conv_layers)):
         h = conv2d(h, conv.weight, conv.bias, (1, 1), "lrelu" if li < 4 else None, 0.1)

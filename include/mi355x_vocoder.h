@@ -379,11 +379,17 @@ int mv_dropout_mask_dev(uint8_t* mask, long n, float p, const long* state_dev, l
  * odd kernels with "same" padding, Cin % 32 == 0, Cout % 16 == 0 (MSD: H = 1; MPD: H = period).
  *   mv_dconv_pack(w [Cout,Cin,kh,kw], flip): MFMA A-fragment order; flip = 1 packs the data-gradient kernel
  *     (taps flipped, channels transposed) - call mv_dconv_cl_fwd with Cin/Cout swapped on the output gradient.
+ *     dtype MV_F32: split operands - every 2 KB fragment holds the hi bf16 image of the weights followed by the lo image
+ *     (bf16(w - hi)), the layout Mma<float>::load_a reads; same mv_dconv_packed_bytes as before (4 bytes per weight).
  *   mv_dconv_cl_fwd: y = act(conv(x) + bias).  act_save (optional, [B][H][W][Cout]): data-gradient mode - the result is
  *     multiplied by LeakyReLU'(.) evaluated on that saved activation, i.e. it is d/d(pre-activation) of the previous layer.
+ *     dtype MV_F32 (fp32 storage, MV_F32 packs): every product is hi*hi + hi*lo + lo*hi of bf16 operands with fp32 accumulation
+ *     (~2^-16 relative), activations staged in LDS as pre-split hi / lo planes; forward, act_save data gradient and the
+ *     zero-padded head alike.  B * H <= 65535.
  *   mv_dhead_*: the Cout = 1 layer (weights as fp32 [kh*kw][C] from mv_conv_out_pack-style transposition).
- *   mv_dconv_wgrad_cl: gw fp32 [Cout][Cin][kh][kw] = sum g x (16-bit storage only; 3x3, and 1xk for k in 1,3,5,7,11,15
- *     with W-dilation dil_w, (k-1)*dil_w <= 64 - the GRC/MRF convs of grc_lora.py:36-41 run through the same kernels);
+ *   mv_dconv_wgrad_cl: gw fp32 [Cout][Cin][kh][kw] = sum g x (16-bit storage: 3x3, and 1xk for k in 1,3,5,7,11,15
+ *     with W-dilation dil_w, (k-1)*dil_w <= 64 - the GRC/MRF convs of grc_lora.py:36-41 run through the same kernels;
+ *     MV_F32: split operands as in mv_dconv_cl_fwd, 3x3 and 1x15 with dil_w = 1 only, otherwise MV_ERR_UNSUPPORTED);
  *     gb (optional, fp32 [Cout]): the bias gradient sum_pos g[pos][o], accumulated from the LDS-resident g tiles;
  *     workspace: mv_dconv_wgrad_workspace_bytes() of device scratch (tap-major partial sums). */
 size_t mv_dconv_packed_bytes(int Cout, int Cin, int kh, int kw, int dtype);
@@ -391,7 +397,7 @@ int mv_dconv_pack(const void* w, int param_dtype, void* packed, int Cout, int Ci
                   void* stream);
 /* n weight tensors packed by one launch.  descs_dev: device array of { const float* src; void* dst; int Cout, Cin, kh, kw, flip, dtype; }
  * (40 bytes each): src = fp32 [Cout][Cin][kh][kw] with Cout % 16 == 0 and Cin % 32 == 0 (no padding), dst = mv_dconv_packed_bytes image,
- * dtype MV_BF16 / MV_F16.  Same result as n mv_dconv_pack calls. */
+ * dtype MV_BF16 / MV_F16 / MV_F32 (split hi + lo images).  Same result as n mv_dconv_pack calls. */
 int mv_dconv_multi_pack(const void* descs_dev, int n, void* stream);
 /* mv_dconv_pack with the operator zero-padded to Coutp x Cinp channels (multiples of 32 for the side that is contracted). */
 int mv_dconv_pack_pad(const void* w, int param_dtype, void* packed, int Cout, int Cin, int kh, int kw, int Coutp, int Cinp,
@@ -424,7 +430,8 @@ size_t mv_dconv_wgrad_workspace_bytes(int Cin, int Cout, int kh, int kw);
 int mv_dconv_wgrad_cl(const void* x, const void* g, float* gw, float* gb, float* workspace, int B, int H, int W, int Cin,
                       int Cout, int kh, int kw, int dil_w, int dtype, void* stream);
 /* The same with a workspace the caller keeps between calls: (Cout*Cin*kh*kw + Cout) floats, ZERO on entry, zero again on exit (the
- * reorder pass clears what it reads), so no fill launch is needed per call.  gb (may be NULL) receives the bias sums. */
+ * reorder pass clears what it reads), so no fill launch is needed per call.  gb (may be NULL) receives the bias sums.  Storage types
+ * and geometries as mv_dconv_wgrad_cl. */
 int mv_dconv_wgrad_cl_pz(const void* x, const void* g, float* gw, float* gb, float* workspace, int B, int H, int W, int Cin,
                          int Cout, int kh, int kw, int dil_w, int dtype, void* stream);
 

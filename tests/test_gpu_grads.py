@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from test_gpu_generator_train_shapes import odconv_transpose_fp64
 from oracle import vocoder_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -306,7 +307,6 @@ def test_odconv_transpose_mfma_data_gradient_vs_fp64(H, dtype, cin, cout, ks, st
     ODConv over rows of `stride` output steps (kernel_size = 2*stride), the bank gradients as per-sample two-tap MFMA
     weight-gradient GEMMs + the alpha-chain reduction.  Checked against an fp64 CPU evaluation of the reference arithmetic
     on the same 16-bit-rounded parameters and input: x.grad, kernels.grad, bias.grad and the attention-head gradients."""
-    import torch.nn.functional as F
     torch.manual_seed(0)
     m = H.ODConvTranspose1d(cin, cout, ks, stride=stride, padding=pad)
     with torch.no_grad():
@@ -315,14 +315,9 @@ def test_odconv_transpose_mfma_data_gradient_vs_fp64(H, dtype, cin, cout, ks, st
     torch.manual_seed(1)
     x = torch.randn(3, cin, T).to(dtype)
     # fp64 reference: alpha = softmax(Wa mean_t x + ba); y = sum_k alpha_k convT(x, W_k) + alpha_k b_k
-    xr = x.double().requires_grad_(True)
-    att = m.kernel_attention[1]
-    Wk, bk, Wa, ba = (t.detach().double().requires_grad_(True) for t in (m.kernels, m.bias, att.weight, att.bias))
-    a = torch.softmax(F.conv1d(xr.mean(2, keepdim=True), Wa, ba).squeeze(-1), dim=1)
-    yr = sum(a[:, k].view(-1, 1, 1) * F.conv_transpose1d(xr, Wk[k], bk[k], stride=stride, padding=pad) for k in range(Wk.shape[0]))
     torch.manual_seed(2)
-    r = torch.randn_like(yr)
-    (yr * r).sum().backward()
+    r = torch.randn(3, cout, (T - 1) * stride - 2 * pad + ks, dtype=torch.float64)
+    yr, gxr, gp = odconv_transpose_fp64(m, x, r, stride, pad)
     md = m.cuda()
     xd = x.cuda().requires_grad_(True)
     y = md(xd)
@@ -332,12 +327,12 @@ def test_odconv_transpose_mfma_data_gradient_vs_fp64(H, dtype, cin, cout, ks, st
     assert OdconvFused(md).dgrad_supported()
     eps = 3e-2 if dtype == torch.bfloat16 else 4e-3
     assert O.rel_l2(y.detach().cpu(), yr.detach()) < eps
-    assert O.rel_l2(xd.grad.cpu(), xr.grad) < eps
+    assert O.rel_l2(xd.grad.cpu(), gxr) < eps
     # bank gradients and the attention chain (d alpha = <per-sample gradient, W_k>) from the MFMA per-sample GEMMs
-    assert O.rel_l2(md.kernels.grad.cpu(), Wk.grad) < eps
-    assert O.rel_l2(md.bias.grad.cpu(), bk.grad) < eps
-    assert O.rel_l2(md.kernel_attention[1].weight.grad.cpu(), Wa.grad) < 3 * eps
-    assert O.rel_l2(md.kernel_attention[1].bias.grad.cpu(), ba.grad) < 3 * eps
+    assert O.rel_l2(md.kernels.grad.cpu(), gp["kernels"]) < eps
+    assert O.rel_l2(md.bias.grad.cpu(), gp["bias"]) < eps
+    assert O.rel_l2(md.kernel_attention[1].weight.grad.cpu(), gp["kernel_attention.1.weight"]) < 3 * eps
+    assert O.rel_l2(md.kernel_attention[1].bias.grad.cpu(), gp["kernel_attention.1.bias"]) < 3 * eps
 
 
 def test_second_design_blocks_grads(H):

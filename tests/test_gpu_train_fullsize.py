@@ -80,6 +80,27 @@ def test_wgrad3x3_training_shapes(ops, P, cin, cout):
     assert _rel(gw, w.grad) < 2e-3 and _rel(gb, bias.grad) < 2e-3, (P, cin, cout, _rel(gw, w.grad), _rel(gb, bias.grad))
 
 
+@pytest.mark.parametrize("Tn", [8192, 4096, 2048])
+@pytest.mark.parametrize("cin,cout", [(32, 64), (64, 128), (128, 256)])
+def test_wgrad_k15_training_shapes(ops, Tn, cin, cout):
+    """MSD k15 weight and bias gradients (dwgrad_launch<bf16,15>) over the whole 64-sample batch against torch autograd on fp32 copies
+    of the same bf16 operands.  At these shapes the kernel's 64 x cdiv(Tn, 128) chunks outnumber its 256 / tiles workgroups, so every
+    workgroup carries its accumulators across several chunks and across sample boundaries (4 to 64 chunks per workgroup)."""
+    torch.manual_seed(1)
+    x = torch.randn(B, 1, Tn, cin, device="cuda").to(DT)
+    g = (torch.randn(B, 1, Tn, cout, device="cuda") / 8).to(DT)
+    gw, gb = ops.dconv_wgrad_cl(x, g, 1, 15, 1, want_bias=True)
+    w = torch.zeros(cout, cin, 1, 15, device="cuda", requires_grad=True)
+    bias = torch.zeros(cout, device="cuda", requires_grad=True)
+    step = 16
+    for i in range(0, B, step):
+        y = torch.nn.functional.conv2d(x[i:i + step].permute(0, 3, 1, 2).float(), w, bias, padding=(0, 7))
+        y.backward(g[i:i + step].permute(0, 3, 1, 2).float())
+    ew, eb = _rel(gw, w.grad), _rel(gb, bias.grad)
+    print(f"[train] k15 wgrad B{B} T{Tn} {cin}->{cout}: w {ew:.2e} b {eb:.2e}")
+    assert ew < 2e-3 and eb < 2e-3, (Tn, cin, cout, ew, eb)
+
+
 def test_full_size_train_step_c3():
     """BASELINE configs[2] at its full size: VocoderTrainer.train_step on the default generator + MPD + MSD, B = 32 clips x 8192
     samples, bf16 activations (what bench.py times).  Finite losses, and the loss dict of the first step (same weights, same batch)

@@ -65,6 +65,21 @@ __device__ float mrf_weff(const MrfRawParams& p, int br, int o, int c, int jj, i
   return acc;
 }
 
+// b_eff = Wp bc + bp of concat row cc (branch br, local o): the bias of v in front of the branch GroupNorm
+template <typename P>
+__device__ float mrf_beff(const MrfRawParams& p, int br, int o) {
+  float v = ld<P>((const P*)p.proj_b[br] + o);
+  for (int op = 0; op < MRF_CPD; ++op)
+    v += ld<P>((const P*)p.proj_w[br] + o * MRF_CPD + op) * ld<P>((const P*)p.conv_b[br] + op);
+  return v;
+}
+
+// The bias tables b_conv and b_fus hold the biases MINUS their GroupNorm group's mean (4-channel groups of v, 8-channel groups of f).
+// A GroupNorm is invariant to a constant added to a whole group, so every kernel below computes the same block - but its accumulators
+// then hold v - p and f - p, p = the mean bias of the group, and the single-pass statistics (sum, sum of squares per workgroup,
+// var = E[x^2] - mu^2 in fp32) are taken about that pivot at no cost in the kernels.  Unshifted, they cancel once a group's mean is a
+// few tens of its stds (error of rstd 1e-5 at mean/std = 30, 5e-4 at 100), and what moves a group's mean in a trained block is the
+// bias in front of the norm.  f is stored shifted too (only its GroupNorm reads it), which also keeps its f16 / hl8 rows small.
 template <typename T, typename P>
 __global__ __launch_bounds__(256) void mrf_pack_kernel(MrfRawParams p, MrfMeta meta, char* __restrict__ out, int rank) {
   constexpr int FS = Mma<T>::NSETS * FRAG_BYTES;
@@ -74,15 +89,20 @@ __global__ __launch_bounds__(256) void mrf_pack_kernel(MrfRawParams p, MrfMeta m
     if (idx >= total) {  // float tables
       const int ti = idx - total, which = ti / 64, cc = ti % 64;
       float v = 0.f;
-      if (which == 2) v = ld<P>((const P*)p.fusion_b + cc);
+      if (which == 2) {
+        const P* fb = (const P*)p.fusion_b + (cc & ~7);
+        float q[8];
+        for (int i = 0; i < 8; ++i) q[i] = ld<P>(fb + i);
+        v = q[cc & 7] - 0.125f * (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])));
+      }
       else if (which == 5) v = ld<P>((const P*)p.norm2_w + cc);
       else if (which == 6) v = ld<P>((const P*)p.norm2_b + cc);
       else if (cc < MRF_NBR * MRF_CPD) {
         const int br = cc / MRF_CPD, o = cc % MRF_CPD;
-        if (which == 0) {  // b_eff = Wp bc + bp
-          v = ld<P>((const P*)p.proj_b[br] + o);
-          for (int op = 0; op < MRF_CPD; ++op)
-            v += ld<P>((const P*)p.proj_w[br] + o * MRF_CPD + op) * ld<P>((const P*)p.conv_b[br] + op);
+        if (which == 0) {  // b_eff minus the mean b_eff of its group (4 consecutive rows: 20 channels per branch = 5 groups)
+          float q[4];
+          for (int i = 0; i < 4; ++i) q[i] = mrf_beff<P>(p, br, (o & ~3) + i);
+          v = q[o & 3] - 0.25f * ((q[0] + q[1]) + (q[2] + q[3]));
         } else if (which == 1) v = ld<P>((const P*)p.res_b[br] + o);
         else if (which == 3) v = ld<P>((const P*)p.norm_w[br] + o);
         else if (which == 4) v = ld<P>((const P*)p.norm_b[br] + o);

@@ -109,7 +109,11 @@ class ModifiedHiFiGANGenerator(nn.Module):
         22 kHz generator (north_star: 1e-3) and above 1e-3 on the 48 kHz one - DESIGN.md section 5.
         mrf_weights="fp16": the three MultiReceptiveFieldBlocks keep fp32 storage and hi + lo (f16) activation operands but use their
         weights as single f16 values - two MFMA products per MAC instead of three (MV_F32_W16; +1.1e-4 in quadrature at 22 kHz,
-        out of tolerance at 48 kHz).  Returns self."""
+        out of tolerance at 48 kHz).  Validated scale window of the stream that enters the chain: rms 2^-12 .. 2^8 (the chain's OUTPUT stays
+        inside 4e-4 against fp64 and equal to the simulation of its formats; default init: 2^-9.5; an unsaturated waveform behind it
+        is at 4e-4 .. 1.1e-3 below 2^-4, where the output conv's bias removes a mean that is large against the signal); above 2^9 the 15-bit rows between
+        the blocks clamp, at 2^14 their f16 plane overflows.  With an unsaturated output (pre-tanh rms 0.3) the mode measures 1.05e-3 -
+        1.09e-3 waveform rel-L2, i.e. above 1e-3 (tests/test_gpu_inference_off_unit_scale.py).  Returns self."""
         if mrf_weights not in (None, "fp16"):
             raise ValueError("mrf_weights must be None or 'fp16'")
         object.__setattr__(self, "_mv_mrf_w16", mrf_weights == "fp16" and through is not None)

@@ -12,7 +12,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import vocoder_oracle as O  # noqa: E402
+from numerics_sim import mrf_blocks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,13 +26,7 @@ def H():
 
 
 def _blocks(H, seed=0):
-    torch.manual_seed(seed)
-    blks = [H.MultiReceptiveFieldBlock(64, 64) for _ in range(3)]
-    for bk in blks:
-        for p in bk.parameters():
-            if p.dim() == 1 and p.numel() in (20, 64):
-                p.data.add_(0.3 * torch.randn_like(p))        # non-trivial GroupNorm affines and biases
-    sds = [{k: v.detach().clone() for k, v in bk.state_dict().items()} for bk in blks]
+    blks, sds = mrf_blocks(seed)                              # shared with tests/test_gpu_inference_off_unit_scale.py
     return [bk.cuda().train(False) for bk in blks], sds
 
 

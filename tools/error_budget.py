@@ -8,7 +8,8 @@ time, so the waveform rel-L2 of every single source - and of any mix - can be re
     python tools/error_budget.py            # 22 kHz default generator, B=2 x 32 frames
     python tools/error_budget.py 48k
 
-Modes: fp32 (no rounding), bf16, fp16, fp16x2 (hi + lo fp16 pair, 22 significant bits), bf16x2, bf16x3.
+Modes: fp32 (no rounding), bf16, fp16, fp16x2 (hi + lo fp16 pair, 22 significant bits), bf16x2, bf16x3, hl8 (the streaming
+chain's rows between its blocks: f16 hi + e4m3 byte of (v - hi) * 2048 clamped to +-448, csrc/mfma.h - 15 significant bits).
 """
 import os
 import sys
@@ -27,6 +28,10 @@ def q(t, mode):
     if mode in ("bf16", "fp16"):
         dt = torch.bfloat16 if mode == "bf16" else torch.float16
         return t.to(dt).float()
+    if mode == "hl8":
+        hi = t.to(torch.float16).float()
+        lo = ((t - hi) * 2048.0).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()    # (the cast alone turns 500 into NaN)
+        return hi + lo / 2048.0
     base, n = mode[:-2], int(mode[-1])
     dt = torch.bfloat16 if base == "bf16" else torch.float16
     acc = torch.zeros_like(t)
@@ -39,9 +44,47 @@ STAGES = ["mel", "input_proj", "up0", "up1", "up2", "up3", "mrf0", "mrf1", "mrf2
 LAYERS = ["input_proj", "up0", "up1", "up2", "up3", "mrf0", "mrf1", "mrf2", "out"]
 
 
-def forward(mel, sd, spk, emo, ups_f, act, wgt, cmode, kloop_layers=("input_proj", "up0"), opmode=None, fmode=None):
+def mrf_forward(x, sd, pre, dil, wm, cm, out_mode, opmode=None, fmode=None):
+    """One MultiReceptiveFieldBlock as mv_mrf_pack + the fused kernels evaluate it, with roundings injected: wm = weight mode (or a
+    dict {conv, res, fus}), cm = mode of the concat, out_mode = storage mode of the output, opmode = MFMA operand view of the stored
+    input (the residual path reads the stored value), fmode = storage mode of the pre-GroupNorm fusion output f."""
+    wmc, wmr, wmf = (wm["conv"], wm["res"], wm["fus"]) if isinstance(wm, dict) else (wm, wm, wm)
+    xs = x                                   # as stored (residual path reads this)
+    if opmode is not None:                   # MFMA operand view of the stored stream
+        x = q(xs, opmode)
+    branches = []
+    for j, d in enumerate(dil):
+        p = f"{pre}conv_layers.{j}."
+        Wc = sd[p + "conv.weight"]
+        out_ch, cin_g, k = Wc.shape
+        G = x.shape[1] // cin_g
+        # folded dense kernel in fp32 (mv_mrf_pack), rounded once
+        Wd = torch.zeros(out_ch, x.shape[1], k, dtype=x.dtype)
+        for o in range(out_ch):
+            g = o // (out_ch // G)
+            Wd[o, g * cin_g:(g + 1) * cin_g] = Wc[o]
+        L = sd[p + "lora_A"] @ sd[p + "lora_B"]
+        Wd[:, :, k // 2] += sd[p + "lora_scaling"] * L.t()
+        Pw = sd[p + "output_projection.weight"][:, :, 0]
+        Weff = torch.einsum("oq,qck->ock", Pw, Wd)
+        beff = Pw @ sd[p + "conv.bias"] + sd[p + "output_projection.bias"]
+        v = F.conv1d(x, q(Weff, wmc), beff, padding=d, dilation=d)
+        w = O.group_norm(v, O.norm_groups_for(out_ch), sd[p + "norm.weight"], sd[p + "norm.bias"])
+        a = O.silu(w)
+        res = F.conv1d(x, q(sd[p + "residual_proj.weight"], wmr), sd[p + "residual_proj.bias"])
+        branches.append(a + res)
+    c = q(torch.cat(branches, 1), cm)
+    f_ = F.conv1d(c, q(sd[pre + "fusion.weight"], wmf), sd[pre + "fusion.bias"])
+    if fmode is not None:
+        f_ = q(f_, fmode)
+    n = O.group_norm(f_, O.norm_groups_for(f_.shape[1]), sd[pre + "norm.weight"], sd[pre + "norm.bias"])
+    return q(n + xs, out_mode)
+
+
+def forward(mel, sd, spk, emo, ups_f, act, wgt, cmode, kloop_layers=("input_proj", "up0"), opmode=None, fmode=None, stages=None):
     """act[stage] = storage/operand mode of that stage's OUTPUT; wgt[layer] = weight mode (an MRF layer may give a dict
-    {conv, res, fus}); cmode[i] = mode of MRF i's concat; fmode = storage mode of the chain's pre-GroupNorm fusion output f."""
+    {conv, res, fus}); cmode[i] = mode of MRF i's concat; fmode = storage mode of the chain's pre-GroupNorm fusion output f;
+    stages = a dict that receives the MRF outputs as stored ("mrf0".."mrf2")."""
     ups, mrfs, cur = O.generator_channel_plan(512, ups_f, 4, ((1, 3, 5),) * 3)
 
     def odconv(x, prefix, name, transposed, **kw):
@@ -64,39 +107,9 @@ def forward(mel, sd, spk, emo, ups_f, act, wgt, cmode, kloop_layers=("input_proj
         x = odconv(x, f"upsample_layers.{i}.0.", f"up{i}", True, stride=f, padding=f // 2, output_padding=f % 2)
         x = q(O.leaky_relu(x, 0.1), act[f"up{i}"])
     for i, (_, _, dil) in enumerate(mrfs):
-        pre = f"mrf_blocks.{i}."
-        wm = wgt[f"mrf{i}"]
-        wmc, wmr, wmf = (wm["conv"], wm["res"], wm["fus"]) if isinstance(wm, dict) else (wm, wm, wm)
-        xs = x                                   # as stored (residual path reads this)
-        if opmode is not None:                   # MFMA operand view of the stored stream
-            x = q(xs, opmode)
-        branches = []
-        for j, d in enumerate(dil):
-            p = f"{pre}conv_layers.{j}."
-            Wc = sd[p + "conv.weight"]
-            out_ch, cin_g, k = Wc.shape
-            G = x.shape[1] // cin_g
-            # folded dense kernel in fp32 (mv_mrf_pack), rounded once
-            Wd = torch.zeros(out_ch, x.shape[1], k)
-            for o in range(out_ch):
-                g = o // (out_ch // G)
-                Wd[o, g * cin_g:(g + 1) * cin_g] = Wc[o]
-            L = sd[p + "lora_A"] @ sd[p + "lora_B"]
-            Wd[:, :, k // 2] += sd[p + "lora_scaling"] * L.t()
-            Pw = sd[p + "output_projection.weight"][:, :, 0]
-            Weff = torch.einsum("oq,qck->ock", Pw, Wd)
-            beff = Pw @ sd[p + "conv.bias"] + sd[p + "output_projection.bias"]
-            v = F.conv1d(x, q(Weff, wmc), beff, padding=d, dilation=d)
-            w = O.group_norm(v, O.norm_groups_for(out_ch), sd[p + "norm.weight"], sd[p + "norm.bias"])
-            a = O.silu(w)
-            res = F.conv1d(x, q(sd[p + "residual_proj.weight"], wmr), sd[p + "residual_proj.bias"])
-            branches.append(a + res)
-        c = q(torch.cat(branches, 1), cmode[i])
-        f_ = F.conv1d(c, q(sd[pre + "fusion.weight"], wmf), sd[pre + "fusion.bias"])
-        if fmode is not None:
-            f_ = q(f_, fmode)
-        n = O.group_norm(f_, O.norm_groups_for(f_.shape[1]), sd[pre + "norm.weight"], sd[pre + "norm.bias"])
-        x = q(n + xs, act[f"mrf{i}"])
+        x = mrf_forward(x, sd, f"mrf_blocks.{i}.", dil, wgt[f"mrf{i}"], cmode[i], act[f"mrf{i}"], opmode, fmode)
+        if stages is not None:
+            stages[f"mrf{i}"] = x
     Wo = sd["output_proj.weight"]
     y = F.conv1d(x, q(Wo, wgt["out"]), sd["output_proj.bias"], padding=Wo.shape[2] // 2)
     return q(torch.tanh(y), act["wave"]), y

@@ -20,6 +20,7 @@ MV_F32_W16P = 4       # the same with the chain's INPUT already in pair rows (mv
 ACT_NONE, ACT_LRELU, ACT_TANH, ACT_SILU = 0, 1, 2, 3
 
 _ERR = {-1: "MV_ERR_ARG (shape/size contract violated)", -2: "MV_ERR_DTYPE", -3: "MV_ERR_UNSUPPORTED"}
+MV_ERR_UNSUPPORTED = -3   # no such variant for this geometry: the callers that have another route compare with it
 
 _CTYPE = {"int": c_int, "long": c_long, "float": c_float, "size_t": ctypes.c_size_t}
 

@@ -11,7 +11,6 @@ ride the wide conv zero-padded to 32 channels.  The default "exact" mode keeps t
 """
 from __future__ import annotations
 
-import weakref
 from ctypes import c_void_p
 
 import torch
@@ -23,27 +22,8 @@ from . import ops
 _P = lambda t: None if t is None else c_void_p(t.data_ptr())
 
 
-class _PackCache:
-    """Packed weights per (parameter, dtype, kind).  Entries are validated against the LIVE parameter object through a
-    weak reference (Python ids and device addresses are recycled once a module is freed) plus its version / the
-    parameter epoch, so a freed module can never alias another one's packed buffer."""
-
-    def __init__(self):
-        self.d = {}
-
-    def _lookup(self, param, kind):
-        key = (id(param), kind)
-        ver = (param._version, ops.param_epoch_of(param), param.data_ptr())
-        hit = self.d.get(key)
-        if hit is not None and hit[0]() is param and hit[1] == ver:
-            return key, ver, hit[2]
-        return key, ver, None
-
-    def _store(self, key, param, ver, buf):
-        if len(self.d) > 1024:
-            self.d = {k: e for k, e in self.d.items() if e[0]() is not None}
-        self.d[key] = (weakref.ref(param), ver, buf)
-        return buf
+class _PackCache(ops.DerivedCache):
+    """Packed weights per (parameter, kind): the builders of the discriminator stacks' MFMA operand images."""
 
     def refresh_owned(self, opt):
         """After `opt.step()` (flat-arena AdamW): re-pack every plain conv pack whose fp32 master belongs to `opt` with ONE launch and
@@ -51,7 +31,7 @@ class _PackCache:
         import numpy as np
         ents = []
         for key, e in self.d.items():
-            kind, p = key[1], e[0]()
+            kind, p = key[1], e[0][0]()
             if (p is None or not isinstance(kind, tuple) or len(kind) != 2 or kind[0] not in (torch.bfloat16, torch.float16, torch.float32)
                     or p.dtype != torch.float32 or not p.is_contiguous() or not opt.owns(p)):
                 continue
@@ -71,60 +51,54 @@ class _PackCache:
             table = torch.from_numpy(d.view(np.uint8).reshape(-1)).to(ents[0][1].device)
             hit = self._mp[id(opt)] = (sig, table)
         N.call("mv_dconv_multi_pack", _P(hit[1]), len(ents), ops._stream())
-        for key, p, buf, _, _ in ents:
-            self.d[key] = (weakref.ref(p), (p._version, ops.param_epoch_of(p), p.data_ptr()), buf)
+        for key, *_ in ents:
+            self.mark_current(key)
         return len(ents)
 
     def get(self, param, dtype, flip):
-        key, ver, buf = self._lookup(param, (dtype, flip))
-        if buf is not None:
-            return buf
-        w = _as4d(param)
-        Cout, Cin, kh, kw = w.shape
-        buf = torch.empty(N.lib().mv_dconv_packed_bytes(Cout, Cin, kh, kw, ops._DT[dtype]), dtype=torch.uint8, device=w.device)
-        wd = w.detach().contiguous()
-        N.call("mv_dconv_pack", _P(wd), ops._DT[wd.dtype], _P(buf), Cout, Cin, kh, kw, int(flip), ops._DT[dtype], ops._stream())
-        return self._store(key, param, ver, buf)
+        return self.lookup(param, (dtype, flip), lambda: _pack(_as4d(param).detach(), dtype, flip))
 
     def head_padded(self, wparam, bparam, dtype, flip, pad_to=32):
         """The [1,C,kh,kw] head zero-padded to `pad_to` output channels, packed for the MFMA conv (forward: flip 0, with the
         padded bias; data gradient: flip 1)."""
-        key, ver, hit = self._lookup(wparam, ("headpad", dtype, flip))
-        if hit is not None:
-            return hit
-        w = _as4d(wparam).detach()
-        C, kh, kw = w.shape[1], w.shape[2], w.shape[3]
-        wp = torch.zeros(pad_to, C, kh, kw, device=w.device, dtype=w.dtype)   # parameter-sized host-side glue
-        wp[0] = w[0]
-        buf = torch.empty(N.lib().mv_dconv_packed_bytes(pad_to, C, kh, kw, ops._DT[dtype]), dtype=torch.uint8, device=w.device)
-        N.call("mv_dconv_pack", _P(wp), ops._DT[wp.dtype], _P(buf), pad_to, C, kh, kw, int(flip), ops._DT[dtype], ops._stream())
-        bias = torch.zeros(pad_to, device=w.device, dtype=dtype)
-        bias[0:1] = bparam.detach().to(dtype)
-        return self._store(key, wparam, ver, (buf, bias))
+        def build():
+            w = _as4d(wparam).detach()
+            wp = torch.zeros(pad_to, *w.shape[1:], device=w.device, dtype=w.dtype)   # parameter-sized host-side glue
+            wp[0] = w[0]
+            buf = _pack(wp, dtype, flip)
+            bias = torch.zeros(pad_to, device=w.device, dtype=dtype)
+            bias[0:1] = bparam.detach().to(dtype)
+            return buf, bias
+        return self.lookup(wparam, ("headpad", dtype, flip), build)
 
     def head_mfma(self, param, dtype):
         """[1,C,kh,kw] head -> the tap-row MFMA operators of mv_dhead_fwd / mv_dhead_dgrad."""
-        key, ver, buf = self._lookup(param, ("headmfma", dtype))
-        if buf is not None:
+        def build():
+            w = _as4d(param).detach().contiguous()
+            C, kh, kw = w.shape[1], w.shape[2], w.shape[3]
+            buf = torch.empty(N.lib().mv_dhead_packed_bytes(C, ops._DT[dtype]), dtype=torch.uint8, device=w.device)
+            N.call("mv_dhead_pack", _P(w), ops._DT[w.dtype], _P(buf), C, kh, kw, ops._DT[dtype], ops._stream())
             return buf
-        w = _as4d(param)
-        C, kh, kw = w.shape[1], w.shape[2], w.shape[3]
-        buf = torch.empty(N.lib().mv_dhead_packed_bytes(C, ops._DT[dtype]), dtype=torch.uint8, device=w.device)
-        wd = w.detach().contiguous()
-        N.call("mv_dhead_pack", _P(wd), ops._DT[wd.dtype], _P(buf), C, kh, kw, ops._DT[dtype], ops._stream())
-        return self._store(key, param, ver, buf)
+        return self.lookup(param, ("headmfma", dtype), build)
 
     def head(self, param):
         """[1,C,kh,kw] (or [1,C,k]) -> fp32 [taps][C]."""
-        key, ver, buf = self._lookup(param, "head")
-        if buf is not None:
-            return buf
-        w = _as4d(param)
-        C, taps = w.shape[1], w.shape[2] * w.shape[3]
-        wt = torch.empty(taps, C, device=w.device, dtype=torch.float32)
-        wd = w.detach().contiguous()
-        N.call("mv_conv_out_pack", _P(wd), ops._DT[wd.dtype], _P(wt), C, taps, ops._stream())
-        return self._store(key, param, ver, wt)
+        def build():
+            w = _as4d(param).detach().contiguous()
+            C, taps = w.shape[1], w.shape[2] * w.shape[3]
+            wt = torch.empty(taps, C, device=w.device, dtype=torch.float32)
+            N.call("mv_conv_out_pack", _P(w), ops._DT[w.dtype], _P(wt), C, taps, ops._stream())
+            return wt
+        return self.lookup(param, "head", build)
+
+
+def _pack(w4, dtype, flip):
+    """[Cout,Cin,kh,kw] -> the MFMA conv's packed image (flip = 1: the data-gradient operator)."""
+    Cout, Cin, kh, kw = w4.shape
+    w4 = w4.contiguous()
+    buf = torch.empty(N.lib().mv_dconv_packed_bytes(Cout, Cin, kh, kw, ops._DT[dtype]), dtype=torch.uint8, device=w4.device)
+    N.call("mv_dconv_pack", _P(w4), ops._DT[w4.dtype], _P(buf), Cout, Cin, kh, kw, int(flip), ops._DT[dtype], ops._stream())
+    return buf
 
 
 _packs = _PackCache()
@@ -165,7 +139,7 @@ class _DiscStack(Function):
                 rc = N.lib().mv_dconv_cl_fwd_head(_P(acts[-1]), _P(_packs.get(params[2 * li], dt, 0)), _P(cast(bs[li])), _P(y),
                                                   _P(_packs.head_mfma(params[8], dt)), _P(zws), hkh, hkw, B, H, W, Cin, Cout, kh, kw,
                                                   N.ACT_LRELU, float(slope), ops._dt(x0), st())
-                if rc != -3:            # MV_ERR_UNSUPPORTED: no 256-row variant for this geometry - separate launches below
+                if rc != N.MV_ERR_UNSUPPORTED:   # no 256-row variant for this geometry - separate launches below
                     N.check(rc, "mv_dconv_cl_fwd_head")
                     head_fused = True
             if not (li == 3 and head_fused):

@@ -34,10 +34,6 @@ _UNFUSED_RES2 = False   # tests: force the conv-by-conv Res2Net chain
 _SKINNY_ROWS = 4096     # up to this many positions the split-K GEMM beats the tiled conv kernel (tools/bench_embed.py)
 
 
-def _sig(mod: nn.Module):
-    return (ops.param_epoch(),) + tuple(t._version for t in mod.state_dict(keep_vars=True).values())
-
-
 def _fold_bn(w: torch.Tensor, b: Optional[torch.Tensor], bn: Optional[nn.BatchNorm1d]):
     """Weights/bias of `bn(conv(x))` in eval mode as one affine map (fp32)."""
     w = w.detach().float()
@@ -78,7 +74,7 @@ class _Affine:
                                                    kind, float(slope), ops._dt(x_cl), ops._stream())
                     if rc == 0:
                         return y
-                    if rc != -3:
+                    if rc != N.MV_ERR_UNSUPPORTED:
                         N.check(rc, "mv_gemm_cl_skinny")
                 return ops.dconv_cl(x_cl.view(1, B * T, C), self.packed, self.bias, self.cout, 1, 1, 1, kind, slope).view(B, T, self.cout)
             return ops.dconv_cl(x_cl, self.packed, self.bias, self.cout, 1, self.ks, self.dil, kind, slope)
@@ -94,15 +90,13 @@ class _Affine:
 
 
 class _Plan:
-    """Folded / packed weights of one module for one dtype; rebuilt when any parameter or buffer changes."""
+    """Folded / packed weights of one module per dtype; rebuilt when any parameter or buffer changes."""
 
     def __init__(self):
-        self.sig, self.dtype, self.items = None, None, None
+        self._cache, self.items = ops.DerivedCache(), None
 
     def get(self, mod, dtype, build):
-        sig = _sig(mod)
-        if self.items is None or self.sig != sig or self.dtype != dtype:
-            self.items, self.sig, self.dtype = build(dtype), sig, dtype
+        self.items = self._cache.lookup(tuple(mod.state_dict(keep_vars=True).values()), dtype, lambda: build(dtype))
         return self.items
 
 

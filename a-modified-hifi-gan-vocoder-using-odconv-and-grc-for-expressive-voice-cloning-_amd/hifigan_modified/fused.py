@@ -17,8 +17,22 @@ from .ops import _zeros, _new_zeros
 _INT3 = ctypes.c_int * 3
 
 
-def _versions(params):
-    return (ops.param_epoch(),) + tuple((id(p), p._version, p.data_ptr()) for p in params)
+def _P(t):
+    return None if t is None else c_void_p(t.data_ptr())
+
+
+class _Workspaces:
+    """Persistent scratch buffers of one launcher, keyed by (bytes, device)."""
+
+    def __init__(self, align=0):
+        self.align, self._d = align, {}
+
+    def ptr(self, nbytes, device):
+        ws = self._d.get((nbytes, device))
+        if ws is None:          # never evicted: a captured HIP graph may have baked this pointer in
+            ws = self._d[(nbytes, device)] = torch.empty(nbytes + self.align, dtype=torch.uint8, device=device)
+        a = self.align
+        return c_void_p((ws.data_ptr() + a - 1) // a * a if a else ws.data_ptr())
 
 
 class MrfFused:
@@ -26,8 +40,8 @@ class MrfFused:
 
     def __init__(self, blk):
         self.blk = blk
-        self._packed = {}     # dtype -> (versions, tensor)
-        self._ws = {}
+        self._packed = ops.DerivedCache()
+        self._ws = _Workspaces()
 
     @staticmethod
     def supported(blk) -> bool:
@@ -57,10 +71,9 @@ class MrfFused:
 
     def packed(self, dtype, device):
         ps = self._params()
-        ver = _versions(ps)
-        hit = self._packed.get(dtype)
-        if hit is not None and hit[0] == ver and hit[1].device == device:
-            return hit[1]
+        return self._packed.lookup(tuple(ps), dtype, lambda: self._pack(ps, dtype, device))
+
+    def _pack(self, ps, dtype, device):
         pd = ps[0].dtype
         if any(p.dtype != pd or not p.is_contiguous() or p.device != device for p in ps):
             raise RuntimeError("MRF parameters must share one dtype, be contiguous and live on the input's device")
@@ -75,9 +88,7 @@ class MrfFused:
         buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
         dil = _INT3(*self.blk.dilations)
         rank = self.blk.conv_layers[0].lora_A.shape[1]
-        N.call("mv_mrf_pack", ctypes.byref(st), ops._DT[pd], dil, rank, c_void_p(buf.data_ptr()), ops._DT[dtype],
-               ops._stream())
-        self._packed[dtype] = (ver, buf)
+        N.call("mv_mrf_pack", ctypes.byref(st), ops._DT[pd], dil, rank, _P(buf), ops._DT[dtype], ops._stream())
         return buf
 
     def forward_cl(self, x_cl, mask=None, mask_scale=1.0):
@@ -86,16 +97,9 @@ class MrfFused:
         assert C == 64 and x_cl.is_contiguous()
         dt = ops._dt(x_cl)
         packed = self.packed(x_cl.dtype, x_cl.device)
-        wsb = N.lib().mv_mrf_workspace_bytes(B, T, dt)
-        key = (wsb, x_cl.device)
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = torch.empty(wsb, dtype=torch.uint8, device=x_cl.device)
-            self._ws[key] = ws                     # never evicted: a captured HIP graph may have baked this pointer in
+        ws = self._ws.ptr(N.lib().mv_mrf_workspace_bytes(B, T, dt), x_cl.device)
         out = torch.empty_like(x_cl)
-        dil = _INT3(*self.blk.dilations)
-        N.call("mv_mrf_block_fwd_cl", c_void_p(x_cl.data_ptr()), c_void_p(out.data_ptr()), c_void_p(packed.data_ptr()),
-               dil, c_void_p(ws.data_ptr()), None if mask is None else c_void_p(mask.data_ptr()), float(mask_scale),
+        N.call("mv_mrf_block_fwd_cl", _P(x_cl), _P(out), _P(packed), _INT3(*self.blk.dilations), ws, _P(mask), float(mask_scale),
                B, T, float(self.blk.norm.eps), dt, ops._stream())
         return out
 
@@ -105,61 +109,35 @@ class MrfChain:
 
     def __init__(self, mrfs):
         self.mrfs = list(mrfs)
-        self._ws = {}
+        self._ws = _Workspaces(align=256)
 
-    def _mode(self, x_cl, w16):
-        """(mv_dtype code, dtype of the packed weight image): w16 = fp32 storage with single-f16 weights (MV_F32_W16)."""
-        if w16:
-            assert x_cl.dtype == torch.float32
-            return N.MV_F32_W16, torch.float16
-        return ops._dt(x_cl), x_cl.dtype
+    def _args(self, x_cl, n, w16, x_pair):
+        """What both entries take of the first n blocks: (packs, dilations, n, workspace) and (B, T, eps, mode code).
+        w16 = fp32 storage with single-f16 weights (MV_F32_W16); x_pair: x_cl already holds pair rows (MV_F32_W16P, w16 only)."""
+        B, T, C = x_cl.shape
+        assert C == 64 and x_cl.is_contiguous() and 1 <= n <= len(self.mrfs) and (w16 or not x_pair)
+        assert not w16 or x_cl.dtype == torch.float32
+        dt, pdt = (N.MV_F32_W16, torch.float16) if w16 else (ops._dt(x_cl), x_cl.dtype)
+        ptrs = (c_void_p * n)(*[m.packed(pdt, x_cl.device).data_ptr() for m in self.mrfs[:n]])
+        dil = (ctypes.c_int * (3 * n))(*[d for m in self.mrfs[:n] for d in m.blk.dilations])
+        base = self._ws.ptr(N.lib().mv_mrf_chain_workspace_bytes(B, T, dt), x_cl.device)
+        return (ptrs, dil, n, base), (B, T, float(self.mrfs[0].blk.norm.eps), N.MV_F32_W16P if x_pair else dt)
 
     def forward_cl(self, x_cl, nblocks=None, w16=False, materialize=True, x_pair=False):
         """x_cl [B, T, 64] contiguous -> output of block nblocks-1 (default: the last), a new tensor.  materialize=False: the
         chain's passes only (what the generator runs in front of its fused output conv) - returns None; bench.py times that."""
-        n = len(self.mrfs) if nblocks is None else nblocks
-        B, T, C = x_cl.shape
-        assert C == 64 and x_cl.is_contiguous() and 1 <= n <= len(self.mrfs)
-        dt, pdt = self._mode(x_cl, w16)
-        packs = [m.packed(pdt, x_cl.device) for m in self.mrfs[:n]]
-        ptrs = (c_void_p * n)(*[p.data_ptr() for p in packs])
-        dil = (ctypes.c_int * (3 * n))(*[d for m in self.mrfs[:n] for d in m.blk.dilations])
-        wsb = N.lib().mv_mrf_chain_workspace_bytes(B, T, dt)
-        key = (wsb, x_cl.device)
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = torch.empty(wsb + 256, dtype=torch.uint8, device=x_cl.device)
-            self._ws[key] = ws                     # never evicted: a captured HIP graph may have baked this pointer in
-        base = (ws.data_ptr() + 255) // 256 * 256
+        chain, shape = self._args(x_cl, len(self.mrfs) if nblocks is None else nblocks, w16, x_pair)
         out = torch.empty_like(x_cl) if materialize else None
-        eps = float(self.mrfs[0].blk.norm.eps)
-        assert not x_pair or w16
-        N.call("mv_mrf_chain_fwd_cl", c_void_p(x_cl.data_ptr()), None if out is None else c_void_p(out.data_ptr()), ptrs, dil, n,
-               c_void_p(base), B, T, eps, N.MV_F32_W16P if x_pair else dt, ops._stream())
+        N.call("mv_mrf_chain_fwd_cl", _P(x_cl), _P(out), *chain, *shape, ops._stream())
         return out
 
     def forward_out_cl(self, x_cl, conv_packed, conv_bias, ks, act, w16=False, x_pair=False):
         """Chain + output projection + activation in one call (mv_mrf_chain_out_fwd_cl): x_cl [B, T, 64] -> wave [B, 1, T].
         x_pair: x_cl holds pair rows (OdconvFused.forward_cl(out_pair=True)); w16 only (MV_F32_W16P)."""
-        n = len(self.mrfs)
-        B, T, C = x_cl.shape
-        assert C == 64 and x_cl.is_contiguous()
-        dt, pdt = self._mode(x_cl, w16)
-        packs = [m.packed(pdt, x_cl.device) for m in self.mrfs]
-        ptrs = (c_void_p * n)(*[p.data_ptr() for p in packs])
-        dil = (ctypes.c_int * (3 * n))(*[d for m in self.mrfs for d in m.blk.dilations])
-        wsb = N.lib().mv_mrf_chain_workspace_bytes(B, T, dt)
-        key = (wsb, x_cl.device)
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = torch.empty(wsb + 256, dtype=torch.uint8, device=x_cl.device)
-            self._ws[key] = ws                     # never evicted: a captured HIP graph may have baked this pointer in
-        base = (ws.data_ptr() + 255) // 256 * 256
-        wave = torch.empty(B, 1, T, device=x_cl.device, dtype=x_cl.dtype)
-        assert not x_pair or w16
-        N.call("mv_mrf_chain_out_fwd_cl", c_void_p(x_cl.data_ptr()), c_void_p(wave.data_ptr()), ptrs, dil, n, c_void_p(base),
-               c_void_p(conv_packed.data_ptr()), float(conv_bias), int(ks), int(act), B, T, float(self.mrfs[0].blk.norm.eps),
-               N.MV_F32_W16P if x_pair else dt, ops._stream())
+        chain, shape = self._args(x_cl, len(self.mrfs), w16, x_pair)
+        wave = torch.empty(x_cl.shape[0], 1, x_cl.shape[1], device=x_cl.device, dtype=x_cl.dtype)
+        N.call("mv_mrf_chain_out_fwd_cl", _P(x_cl), _P(wave), *chain, _P(conv_packed), float(conv_bias), int(ks), int(act), *shape,
+               ops._stream())
         return wave
 
 
@@ -177,7 +155,7 @@ class OdconvFused:
     def __init__(self, mod):
         self.mod = mod
         self.transposed = bool(getattr(mod, "_transposed", False))
-        self._packed = {}
+        self._packed = ops.DerivedCache()
 
     def geometry(self):
         m = self.mod
@@ -195,22 +173,9 @@ class OdconvFused:
         return stride == 1
 
     def packed(self, dtype, device):
-        w = self.mod.kernels
-        ver = (w._version, w.data_ptr(), ops.param_epoch())
-        hit = self._packed.get(dtype)
-        if hit is not None and hit[0] == ver and hit[1].device == device:
-            return hit[1]
         cin, cout, ks, stride, pad, dil, tr, K = self.geometry()
-        nbytes = N.lib().mv_odconv_cl_packed_bytes(cin, cout, ks, stride, tr, K, ops._DT[dtype])
-        if nbytes == 0:
-            raise RuntimeError("odconv_cl: unsupported geometry")
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        wd = w.detach()
-        wd = wd if wd.is_contiguous() else wd.contiguous()
-        N.call("mv_odconv_cl_pack", c_void_p(wd.data_ptr()), ops._DT[wd.dtype], c_void_p(buf.data_ptr()), cin, cout, ks,
-               stride, tr, K, ops._DT[dtype], ops._stream())
-        self._packed[dtype] = (ver, buf)
-        return buf
+        w = self.mod.kernels
+        return self._packed.lookup(w, dtype, lambda: odconv_pack(w.detach(), cin, cout, ks, stride, tr, K, dtype, device))
 
     def dgrad_supported(self) -> bool:
         """Data gradient on the fused kernel: transposed layers with kernel_size = 2*stride (every upsampler of the generator)."""
@@ -220,24 +185,15 @@ class OdconvFused:
 
     def packed_dgrad(self, dtype, device):
         """The adjoint operator (2-tap stride-1 ODConv over rows of `stride` output steps), packed for mv_odconv_cl_fwd."""
-        w = self.mod.kernels
-        ver = (w._version, w.data_ptr(), ops.param_epoch())
-        hit = self._packed.get(("dgrad", dtype))
-        if hit is not None and hit[0] == ver and hit[1].device == device:
-            return hit[1]
         cin, cout, ks, stride, pad, dil, tr, K = self.geometry()
-        wd = w.detach()
-        wd = wd if wd.is_contiguous() else wd.contiguous()
-        adj = torch.empty(K, cin, stride * cout, 2, device=device, dtype=wd.dtype)
-        P = lambda t: c_void_p(t.data_ptr())
-        N.call("mv_odconvT_adjoint_weights", P(wd), P(adj), K, cin, cout, ks, stride, ops._DT[wd.dtype], ops._stream())
-        nbytes = N.lib().mv_odconv_cl_packed_bytes(stride * cout, cin, 2, 1, 0, K, ops._DT[dtype])
-        if nbytes == 0:
-            raise RuntimeError("odconv_cl: unsupported adjoint geometry")
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        N.call("mv_odconv_cl_pack", P(adj), ops._DT[adj.dtype], P(buf), stride * cout, cin, 2, 1, 0, K, ops._DT[dtype], ops._stream())
-        self._packed[("dgrad", dtype)] = (ver, buf)
-        return buf
+        w = self.mod.kernels
+
+        def build():
+            wd = w.detach().contiguous()
+            adj = torch.empty(K, cin, stride * cout, 2, device=device, dtype=wd.dtype)
+            N.call("mv_odconvT_adjoint_weights", _P(wd), _P(adj), K, cin, cout, ks, stride, ops._DT[wd.dtype], ops._stream())
+            return odconv_pack(adj, stride * cout, cin, 2, 1, 0, K, dtype, device)
+        return self._packed.lookup(w, ("dgrad", dtype), build)
 
     def pad_grad(self, g, Tin):
         """g [B,Cout,Tout] (NCT) -> the time-padded channels-last gradient [B][(Tin+1)*stride][Cout]: row q*stride + r holds
@@ -254,12 +210,11 @@ class OdconvFused:
         """padded gradient -> gx [B,Cin,Tin] (NCT): the alpha-aggregated adjoint conv on the MFMA kernel (None: tile too wide)."""
         cin, cout, ks, stride, pad, dil, tr, K = self.geometry()
         B = gp.shape[0]
-        P = lambda t: None if t is None else c_void_p(t.data_ptr())
         gx_cl = torch.empty(B, Tin, cin, device=gp.device, dtype=gp.dtype)
-        rc = N.lib().mv_odconv_cl_fwd(P(gp), P(self.packed_dgrad(gp.dtype, gp.device)), None, P(alpha), None, 0, None, None, None, 0,
-                                      P(gx_cl), None, B, stride * cout, Tin + 1, cin, Tin, 2, 1, 0, 1, 0, K, int(N.ACT_NONE), 0.1,
+        rc = N.lib().mv_odconv_cl_fwd(_P(gp), _P(self.packed_dgrad(gp.dtype, gp.device)), None, _P(alpha), None, 0, None, None, None, 0,
+                                      _P(gx_cl), None, B, stride * cout, Tin + 1, cin, Tin, 2, 1, 0, 1, 0, K, int(N.ACT_NONE), 0.1,
                                       ops._dt(gp), ops._stream())
-        if rc == -3:                         # MV_ERR_UNSUPPORTED: tile does not fit LDS (very wide adjoint input): the caller uses the generic HIP kernel
+        if rc == N.MV_ERR_UNSUPPORTED:       # tile does not fit LDS (very wide adjoint input): the caller uses the generic HIP kernel
             return None
         N.check(rc, "mv_odconv_cl_fwd")
         return ops.ntc_to_nct(gx_cl)
@@ -269,13 +224,12 @@ class OdconvFused:
         the alpha-chain reduction); None when the shape is outside the kernel's envelope."""
         cin, cout, ks, stride, pad, dil, tr, K = self.geometry()
         B, Tin, _ = x_cl.shape
-        P = lambda t: c_void_p(t.data_ptr())
         gw = torch.empty(K, cin, cout, ks, device=x_cl.device, dtype=torch.float32)
         galpha = _zeros(B, K, device=x_cl.device, dtype=torch.float32)
         ws = torch.empty(N.lib().mv_odconvT_wgrad_workspace_bytes(B, cin, cout, ks, K, ops._dt(x_cl)), dtype=torch.uint8, device=x_cl.device)
-        rc = N.lib().mv_odconvT_wgrad_mfma(P(x_cl), P(gp), P(wk), P(alpha), P(gw), P(galpha), P(ws), B, Tin, cin, cout, ks, stride, K,
+        rc = N.lib().mv_odconvT_wgrad_mfma(_P(x_cl), _P(gp), _P(wk), _P(alpha), _P(gw), _P(galpha), _P(ws), B, Tin, cin, cout, ks, stride, K,
                                            ops._dt(x_cl), ops._stream())
-        if rc == -3:
+        if rc == N.MV_ERR_UNSUPPORTED:
             return None
         N.check(rc, "mv_odconvT_wgrad_mfma")
         return gw, galpha
@@ -289,11 +243,9 @@ class OdconvFused:
         """floats per sample of the partial-sum buffer (`pooled_out`) this layer's launch writes for its consumer's attention.
         in_f16: the launch is the mixed mode's first fp32 stage reading the fp16 stream (mv_odconv_cl_fwd_in16)."""
         cin, cout, ks, stride, pad, dil, tr, K = self.geometry()
-        n = N.lib().mv_odconv_cl_pool_floats_in(B, cin, Tin, cout, self.out_len(Tin), ks, stride, pad, dil, int(tr), K, int(act),
-                                                int(has_film), ops._DT[dtype], int(in_f16))
-        if n == 0 and in_f16:                # no input-widening variant for this geometry: forward_cl casts and takes the plain entry
-            n = N.lib().mv_odconv_cl_pool_floats_in(B, cin, Tin, cout, self.out_len(Tin), ks, stride, pad, dil, int(tr), K, int(act),
-                                                    int(has_film), ops._DT[dtype], 0)
+        floats = lambda f16: N.lib().mv_odconv_cl_pool_floats_in(B, cin, Tin, cout, self.out_len(Tin), ks, stride, pad, dil, int(tr), K,
+                                                                 int(act), int(has_film), ops._DT[dtype], f16)
+        n = (in_f16 and floats(1)) or floats(0)      # no input-widening variant for this geometry: forward_cl casts and takes the plain entry
         if n == 0:
             raise RuntimeError("odconv_cl: unsupported geometry")
         return n
@@ -311,37 +263,37 @@ class OdconvFused:
         assert C == cin and x_cl.is_contiguous()
         Tout = self.out_len(Tin)
         att = m.kernel_attention[1]
-        P = lambda t: None if t is None else c_void_p(t.data_ptr())
-        if storage is not None and storage != x_cl.dtype:
-            if storage == torch.float32 and x_cl.dtype == torch.float16 and film_proj is None and not out_pair:
-                y = torch.empty(B, Tout, cout, device=x_cl.device, dtype=storage)
-                rc = N.lib().mv_odconv_cl_fwd_in16(P(x_cl), P(self.packed(storage, x_cl.device)), P(cache.get(m.bias, storage)), P(alpha),
-                                                   P(pooled_in), 0 if pooled_in is None else pooled_in.shape[1],
-                                                   P(cache.get(att.weight, storage)), P(cache.get(att.bias, storage)), P(y), P(pooled_out),
-                                                   B, cin, Tin, cout, Tout, ks, stride, pad, dil, int(tr), K, int(act), float(slope),
-                                                   ops._stream())
-                if rc != -3:                                   # MV_ERR_UNSUPPORTED: no input-widening variant for this geometry
+        sdt = x_cl.dtype if storage is None else storage
+        y = torch.empty(B, Tout, cout, device=x_cl.device, dtype=sdt)
+        # the three entries share everything but the input in front, and the FiLM pair between the two halves (plain entry only)
+        front = (_P(self.packed(sdt, x_cl.device)), _P(cache.get(m.bias, sdt)), _P(alpha), _P(pooled_in),
+                 0 if pooled_in is None else pooled_in.shape[1], _P(cache.get(att.weight, sdt)), _P(cache.get(att.bias, sdt)))
+        back = (_P(y), _P(pooled_out), B, cin, Tin, cout, Tout, ks, stride, pad, dil, int(tr), K, int(act), float(slope))
+        if sdt != x_cl.dtype:
+            if sdt == torch.float32 and x_cl.dtype == torch.float16 and film_proj is None and not out_pair:
+                rc = N.lib().mv_odconv_cl_fwd_in16(_P(x_cl), *front, *back, ops._stream())
+                if rc != N.MV_ERR_UNSUPPORTED:                 # (unsupported: no input-widening variant for this geometry)
                     N.check(rc, "mv_odconv_cl_fwd_in16")
                     return y
-            x_cl = ops.cast(x_cl, storage)
-        y = torch.empty(B, Tout, cout, device=x_cl.device, dtype=x_cl.dtype)
-        if out_pair:
-            if x_cl.dtype == torch.float32 and film_proj is None:
-                rc = N.lib().mv_odconv_cl_fwd_pair(P(x_cl), P(self.packed(x_cl.dtype, x_cl.device)), P(cache.get(m.bias, x_cl.dtype)), P(alpha),
-                                                   P(pooled_in), 0 if pooled_in is None else pooled_in.shape[1],
-                                                   P(cache.get(att.weight, x_cl.dtype)), P(cache.get(att.bias, x_cl.dtype)), P(y), P(pooled_out),
-                                                   B, cin, Tin, cout, Tout, ks, stride, pad, dil, int(tr), K, int(act), float(slope),
-                                                   ops._stream())
-                if rc != -3:                                   # MV_ERR_UNSUPPORTED: no pair-row variant for this geometry
-                    N.check(rc, "mv_odconv_cl_fwd_pair")
-                    return y, True
-            return self.forward_cl(x_cl, cache, alpha, pooled_in, film_proj, film_F, pooled_out, act, slope), False
-        N.call("mv_odconv_cl_fwd", P(x_cl), P(self.packed(x_cl.dtype, x_cl.device)), P(cache.get(m.bias, x_cl.dtype)),
-               P(alpha), P(pooled_in), 0 if pooled_in is None else pooled_in.shape[1],
-               P(cache.get(att.weight, x_cl.dtype)), P(cache.get(att.bias, x_cl.dtype)),
-               P(film_proj), int(film_F), P(y), P(pooled_out), B, cin, Tin, cout, Tout, ks, stride, pad, dil, int(tr), K,
-               int(act), float(slope), ops._dt(x_cl), ops._stream())
-        return y
+            x_cl = ops.cast(x_cl, sdt)
+        if out_pair and sdt == torch.float32 and film_proj is None:
+            rc = N.lib().mv_odconv_cl_fwd_pair(_P(x_cl), *front, *back, ops._stream())
+            if rc != N.MV_ERR_UNSUPPORTED:                     # (unsupported: no pair-row variant for this geometry)
+                N.check(rc, "mv_odconv_cl_fwd_pair")
+                return y, True
+        N.call("mv_odconv_cl_fwd", _P(x_cl), *front, _P(film_proj), int(film_F), *back, ops._dt(x_cl), ops._stream())
+        return (y, False) if out_pair else y
+
+
+def odconv_pack(w, cin, cout, ks, stride, tr, K, dtype, device):
+    """Kernel banks [K, ...] (K = 1: one plain conv weight) -> the packed image mv_odconv_cl_fwd reads, in `dtype`."""
+    nbytes = N.lib().mv_odconv_cl_packed_bytes(cin, cout, ks, stride, tr, K, ops._DT[dtype])
+    if nbytes == 0:
+        raise RuntimeError(f"odconv_cl: unsupported geometry (cin {cin}, cout {cout}, ks {ks}, stride {stride}, transposed {tr}, K {K})")
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    w = w.contiguous()
+    N.call("mv_odconv_cl_pack", _P(w), ops._DT[w.dtype], _P(buf), cin, cout, ks, stride, tr, K, ops._DT[dtype], ops._stream())
+    return buf
 
 
 _GEN_PAIR = os.environ.get("MV_GEN_PAIR", "0") == "1"
@@ -358,7 +310,7 @@ class GeneratorFused:
         self.mrfs = [mrf_fused_for(b) for b in gen.mrf_blocks]
         eps = {b.norm.eps for b in gen.mrf_blocks} | {g.norm.eps for b in gen.mrf_blocks for g in b.conv_layers}
         self.chain = MrfChain(self.mrfs) if (self.mrfs and all(m is not None for m in self.mrfs) and len(eps) == 1) else None
-        self._wt = {}
+        self._wt = ops.DerivedCache()
 
     def supported(self) -> bool:
         g = self.gen
@@ -368,17 +320,14 @@ class GeneratorFused:
 
     def out_weights(self, device):
         w, b = self.gen.output_proj.weight, self.gen.output_proj.bias
-        ver = (w._version, w.data_ptr(), b._version, ops.param_epoch())
-        hit = self._wt.get("w")
-        if hit is not None and hit[0] == ver and hit[1].device == device:
-            return hit[1], hit[2]
-        C, ks = w.shape[1], w.shape[2]
-        wt = torch.empty(N.lib().mv_conv_out_packed_bytes(C, ks), device=device, dtype=torch.uint8)   # fp32 | bf16 | f16 images
-        wd = w.detach().contiguous()
-        N.call("mv_conv_out_pack_all", c_void_p(wd.data_ptr()), ops._DT[wd.dtype], c_void_p(wt.data_ptr()), C, ks, ops._stream())
-        bias = float(b.detach().float().item())   # host read of one scalar, once per weight version
-        self._wt["w"] = (ver, wt, bias)
-        return wt, bias
+
+        def build():
+            C, ks = w.shape[1], w.shape[2]
+            wt = torch.empty(N.lib().mv_conv_out_packed_bytes(C, ks), device=device, dtype=torch.uint8)   # fp32 | bf16 | f16 images
+            wd = w.detach().contiguous()
+            N.call("mv_conv_out_pack_all", _P(wd), ops._DT[wd.dtype], _P(wt), C, ks, ops._stream())
+            return wt, float(b.detach().float().item())   # host read of one scalar, once per weight version
+        return self._wt.lookup((w, b), "out", build)
 
     def forward(self, mel, speaker_emb=None, emotion_emb=None, cache=None, return_stages=False):
         g = self.gen
@@ -405,7 +354,6 @@ class GeneratorFused:
                                        in_f16=(j >= 1 and sdt(j) == torch.float32 and sdt(j - 1) == torch.float16)))
             T_ = pr.out_len(T_)
         nflat = sum(B * n for n in lens)
-        P = lambda t: None if t is None else c_void_p(t.data_ptr())
         fp = g.final_film.condition_projection
         F = g.final_film.feature_dim if has_cond else 0
         # one launch: attention of input_proj, the channels-last copy of the mel, the FiLM projection, the zero fill
@@ -418,12 +366,12 @@ class GeneratorFused:
         idt = mel.dtype
         spk = None if speaker_emb is None else ops.cast(speaker_emb, idt).contiguous()
         emo = None if emotion_emb is None else ops.cast(emotion_emb, idt).contiguous()
-        rc = N.lib().mv_gen_prologue_in(P(mel), P(cache.get(att.weight, d0)), P(cache.get(att.bias, d0)), P(spk), P(emo),
-                                        P(cache.get(fp.weight, d0)) if has_cond else None, P(cache.get(fp.bias, d0)) if has_cond else None,
-                                        P(alpha0), P(x), P(film_proj), None, 0, B, mel.shape[1], mel.shape[2], K0,
+        rc = N.lib().mv_gen_prologue_in(_P(mel), _P(cache.get(att.weight, d0)), _P(cache.get(att.bias, d0)), _P(spk), _P(emo),
+                                        _P(cache.get(fp.weight, d0)) if has_cond else None, _P(cache.get(fp.bias, d0)) if has_cond else None,
+                                        _P(alpha0), _P(x), _P(film_proj), None, 0, B, mel.shape[1], mel.shape[2], K0,
                                         0 if spk is None else spk.shape[1], 0 if emo is None else emo.shape[1], fp.in_features, 2 * F,
                                         ops._DT[idt], ops._DT[d0], ops._stream())
-        if rc == -3:    # MV_ERR_UNSUPPORTED: a long utterance does not fit one workgroup's LDS - separate launches
+        if rc == N.MV_ERR_UNSUPPORTED:    # a long utterance does not fit one workgroup's LDS - separate launches
             mel = ops.cast(mel, d0)
             alpha0 = ops.odconv_attn(mel, cache.get(att.weight, d0).view(K0, C0), cache.get(att.bias, d0))
             x = ops.nct_to_ntc(mel)

@@ -54,29 +54,21 @@ def cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return y
 
 
-_EPOCH = [0]
-
-
-_FINE = [0]             # bumps that are not attributed to one flat-arena optimizer (broadcast, load)
+_EPOCH = [0]             # every bump
+_FINE = [0]              # bumps that are not attributed to one flat-arena optimizer (broadcast, load, graph capture)
+_SHADOW_OWNERS = {}      # id(parameter) -> weakref(flat-arena optimizer holding a 16-bit shadow of it)
 
 
 def bump_param_epoch(owner=None):
     """Called by code that updates parameters in place behind torch's back (flat-arena AdamW, broadcast): invalidates cached
-    casts / packed weights.  `owner` (a flat-arena optimizer): only ITS parameters changed - caches that ask `param_epoch_of`
-    keep the other optimizer's entries (the discriminator packs survive the generator's step and vice versa); `param_epoch()`
-    still moves on every bump for the coarse caches."""
+    casts / packed weights.  `owner` (a flat-arena optimizer) promises that only ITS parameters changed: the entries of the other
+    optimizer's parameters stay (the discriminator packs survive the generator's step and vice versa).  Without an owner every
+    entry is dropped."""
     _EPOCH[0] += 1
     if owner is None:
         _FINE[0] += 1
     else:
         owner._epoch = getattr(owner, "_epoch", 0) + 1
-
-
-def param_epoch():
-    return _EPOCH[0]
-
-
-_SHADOW_OWNERS = {}     # id(parameter) -> weakref(flat-arena optimizer holding a 16-bit shadow of it)
 
 
 def param_epoch_of(p):
@@ -94,13 +86,48 @@ def register_shadow_owner(opt, params):
         _SHADOW_OWNERS[id(p)] = ref
 
 
-class _ParamCache:
-    """Casts of parameters to the activation dtype.  An entry is valid only for the very same tensor
-    object (weak reference - ids are recycled once a module is freed) at the same ``_version``, so an
-    optimizer step (in-place update -> version bump) or ``load_state_dict`` invalidates it."""
+def param_state(*ps):
+    """The staleness key of every buffer derived from parameters: per tensor (in-place version, storage address, device, epoch).
+    Equal states of the SAME tensor objects mean the same contents: an optimizer step or load_state_dict moves the version, a
+    `.data` reassignment or a `.to(device)` the address / device, a write behind torch's back the epoch (bump_param_epoch)."""
+    return tuple([(p._version, p.data_ptr(), p.device, param_epoch_of(p)) for p in ps])
+
+
+class DerivedCache:
+    """tag x parameter(s) -> a buffer derived from them (a cast, a packed weight image, ...).  An entry is
+    (weak references to the keyed tensors, their param_state, value) and hits only for the very same tensor objects (ids and
+    device addresses are recycled once a module is freed) in an equal state.  The builder is the caller's."""
+
+    def __init__(self, prune_at=1024):
+        self.d = {}
+        self.prune_at = prune_at
+
+    def lookup(self, params, tag, build):
+        """The value cached under `tag` for `params` (one tensor or a tuple of them); `build()` makes it on a miss."""
+        ps = params if isinstance(params, tuple) else (params,)
+        key, state = (tuple([id(p) for p in ps]), tag), param_state(*ps)
+        hit = self.d.get(key)
+        if hit is not None and hit[1] == state and all([r() is p for r, p in zip(hit[0], ps)]):
+            return hit[2]
+        return self._store(key, ps, state, build())
+
+    def mark_current(self, key):
+        """The caller has just rewritten the value of entry `key` from its (live) parameters in place."""
+        refs, _, value = self.d[key]
+        self.d[key] = (refs, param_state(*[r() for r in refs]), value)
+
+    def _store(self, key, ps, state, value):
+        if len(self.d) > self.prune_at:      # drop entries whose parameters are gone
+            self.d = {k: e for k, e in self.d.items() if all(r() is not None for r in e[0])}
+        self.d[key] = (tuple(weakref.ref(p) for p in ps), state, value)
+        return value
+
+
+class _ParamCache(DerivedCache):
+    """Casts of parameters to the activation dtype."""
 
     def __init__(self):
-        self._d = {}
+        super().__init__(prune_at=4096)
 
     def get(self, p: Optional[torch.Tensor], dtype: torch.dtype):
         if p is None:
@@ -116,15 +143,7 @@ class _ParamCache:
                 v = opt.shadow_view(p, dtype)      # validates that id(p) still names the very parameter it registered
                 if v is not None:
                     return v
-        key = (id(p), dtype)
-        hit = self._d.get(key)
-        if hit is not None and hit[0]() is p and hit[1] == (p._version, _EPOCH[0]) and hit[2].device == p.device:
-            return hit[2]
-        v = cast(p.detach(), dtype)
-        if len(self._d) > 4096:  # drop entries whose parameter is gone
-            self._d = {k: e for k, e in self._d.items() if e[0]() is not None}
-        self._d[key] = (weakref.ref(p), (p._version, _EPOCH[0]), v)
-        return v
+        return self.lookup(p, dtype, lambda: cast(p.detach(), dtype))
 
 
 def odconv_attn(x, w, bias, want_pooled=False):

@@ -52,7 +52,7 @@ class _ConvFused:
     def __init__(self, conv):
         self.conv = conv
         self.transposed = isinstance(conv, nn.ConvTranspose1d)
-        self._packed = {}
+        self._packed = ops.DerivedCache()
         self._ones = {}
 
     def geometry(self):
@@ -69,23 +69,10 @@ class _ConvFused:
         return cout % 16 == 0 and s == 1 and 2 * pad == dil * (ks - 1)
 
     def packed(self, dtype, device):
-        from ctypes import c_void_p
-        w = self.conv.weight
-        ver = (w._version, w.data_ptr(), ops.param_epoch())
-        hit = self._packed.get(dtype)
-        if hit is not None and hit[0] == ver and hit[1].device == device:
-            return hit[1]
+        from .fused import odconv_pack
         cin, cout, ks, s, pad, dil = self.geometry()
-        tr = int(self.transposed)
-        nbytes = N.lib().mv_odconv_cl_packed_bytes(cin, cout, ks, s, tr, 1, ops._DT[dtype])
-        if nbytes == 0:
-            raise RuntimeError("plain HiFi-GAN conv: unsupported geometry")
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        wd = w.detach().contiguous()                      # [Cout, Cin, ks] / [Cin, Cout, ks] = one bank
-        N.call("mv_odconv_cl_pack", c_void_p(wd.data_ptr()), ops._DT[wd.dtype], c_void_p(buf.data_ptr()), cin, cout, ks, s, tr, 1,
-               ops._DT[dtype], ops._stream())
-        self._packed[dtype] = (ver, buf)
-        return buf
+        w = self.conv.weight                              # [Cout, Cin, ks] / [Cin, Cout, ks] = one bank
+        return self._packed.lookup(w, dtype, lambda: odconv_pack(w.detach(), cin, cout, ks, s, int(self.transposed), 1, dtype, device))
 
     def __call__(self, x_cl, act=N.ACT_NONE, slope=0.1):
         """x_cl [B, T, Cin] channels-last -> act(conv(x)) [B, T', Cout] channels-last."""

@@ -261,6 +261,112 @@ __global__ __launch_bounds__(256) void multi_gather_kernel(const GatherDesc* __r
   }
 }
 
+// the accumulating form (gradient accumulation: micro-steps 2..N of a window): flat[dst_off + i] += src[i], one fp32 add per element.
+// A NULL source adds nothing; like the gather above it never touches the padding words between parameters, which therefore stay zero
+// from the arena's allocation on (grad_norm_partial_kernel reads them as part of its slice).
+__global__ __launch_bounds__(256) void multi_gather_acc_kernel(const GatherDesc* __restrict__ descs, float* __restrict__ flat, int chunk) {
+  const GatherDesc d = descs[blockIdx.y];
+  const long beg = (long)blockIdx.x * chunk;
+  if (d.src == nullptr || beg >= d.n) return;
+  const long end = beg + chunk < d.n ? beg + chunk : d.n;
+  for (long i = beg + threadIdx.x; i < end; i += blockDim.x) {
+    float v;
+    if (d.dtype == MV_F32) v = ((const float*)d.src)[i];
+    else if (d.dtype == MV_BF16) v = ld<bf16>((const bf16*)d.src + i);
+    else v = ld<f16>((const f16*)d.src + i);
+    flat[d.dst_off + i] += v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------- gradient norm + clip coefficient
+// torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False) over one fp32 arena slice, in two launches and without
+// floating-point atomics, so the same input gives the same bits on every run:
+//   stage 1: a FIXED grid of GN_GRID workgroups x 256 threads, grid-stride over 16-byte groups; one double partial per workgroup
+//   stage 2: one workgroup adds the GN_GRID partials in a fixed order (double) and writes
+//            out[0] = norm = |pre_scale| * sqrt(sum g^2),  out[1] = coef = min(1, max_norm / (norm + 1e-6))   (fp32, torch's formula)
+// Longest chain of dependent fp32 additions: GN_FLUSH + 2 = 34.  A thread squares into four independent fp32 accumulators (one per
+// component of its 16-byte load: a chain of at most GN_FLUSH = 32 adds each), folds them with two more adds and moves the result into
+// a double; everything behind that - the rest of the thread's sweep, the wave butterfly, the cross-wave and cross-workgroup sums -
+// is double, at any arena length.  All terms are non-negative, so the fp32 part's relative error is at most 34 * 2^-24 = 2e-6.
+constexpr int GN_GRID = 1024, GN_FLUSH = 32;
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, long n, double* __restrict__ partials) {
+  __shared__ double red[4];
+  const long n4 = n >> 2, stride = (long)gridDim.x * blockDim.x;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  double acc = 0.0;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  while (i < n4) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int k = 0; k < GN_FLUSH && i < n4; ++k, i += stride) {
+      const float4 v = g4[i];
+      a0 += v.x * v.x; a1 += v.y * v.y; a2 += v.z * v.z; a3 += v.w * v.w;
+    }
+    acc += (double)((a0 + a1) + (a2 + a3));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {      // a slice length that is no multiple of 4 (the arena's own is one of 8)
+    const float v = g[(n4 << 2) + threadIdx.x];
+    acc += (double)(v * v);
+  }
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, int n_partials, float pre_scale,
+                                                               const float* __restrict__ max_norm_dev, float max_norm,
+                                                               float* __restrict__ out) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_partials; i += blockDim.x) acc += partials[i];
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sum = (red[0] + red[1]) + (red[2] + red[3]);
+    const float norm = (float)(fabs((double)pre_scale) * sqrt(sum));
+    const float mx = max_norm_dev ? max_norm_dev[0] : max_norm;
+    const float c = mx / (norm + 1e-6f);
+    out[0] = norm;
+    out[1] = c > 1.f ? 1.f : c;          // (a NaN norm stays a NaN coefficient, an infinite one gives 0: torch.clamp(max=1))
+  }
+}
+
+// ------------------------------------------------------------------------------------------- AdamW with the clip coefficient
+// adamw_kernel / adamw_hp_kernel with g multiplied by gscale * coef[0] (coef: the device slot grad_norm_finish_kernel wrote).  Every
+// per-step input comes either by value (the eager step: bias corrections formed on the host like mv_adamw_flat's) or from device
+// memory (the captured step: hp / step like mv_adamw_flat_hp's).  gscale * 1.0f is gscale, so with a coefficient of exactly 1 the
+// update has the bits of the unclipped kernel of the same form.
+__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, long n, const float* __restrict__ hp,
+                                                         const int* __restrict__ step, float lr, float b1, float b2, float eps,
+                                                         float wd, float bc1, float bc2, float gscale_,
+                                                         const float* __restrict__ coef) {
+  if (hp) { lr = hp[0]; b1 = hp[1]; b2 = hp[2]; eps = hp[3]; wd = hp[4]; }
+  if (step) {
+    const float t = (float)(*step);
+    bc1 = 1.f - powf(b1, t); bc2 = 1.f - powf(b2, t);
+  }
+  const float gscale = gscale_ * coef[0];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float gr = g[i] * gscale;
+    float pi = p[i] * (1.f - lr * wd);
+    const float mi = b1 * m[i] + (1.f - b1) * gr;
+    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    p[i] = pi;
+  }
+}
+
 // ------------------------------------------------------------------------------------------- log-mel spectrogram loss
 // frames: reflect-pad (n_fft-hop)/2, hop, periodic Hann; |rFFT| (power-of-two n_fft: radix-2 FFT of the frame in LDS, forward and
 // adjoint; otherwise a direct O(N^2) DFT with an exact (k*n mod N) twiddle table), mel = fb @ mag, logmel = log(max(mel, clamp)); loss = weight * mean |logmel - target|.
@@ -523,6 +629,47 @@ extern "C" int mv_multi_gather(const void* descs_dev, int n_tensors, long max_le
   const int chunk = 16384;
   dim3 grid((unsigned)((max_len + chunk - 1) / chunk), n_tensors);
   hipLaunchKernelGGL(multi_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const GatherDesc*)descs_dev, flat, chunk);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_multi_gather_acc(const void* descs_dev, int n_tensors, long max_len, float* flat, void* stream) {
+  MV_CHECK_ARG(descs_dev && flat && n_tensors > 0 && n_tensors <= 65535 && max_len > 0);
+  const int chunk = 16384;
+  dim3 grid((unsigned)((max_len + chunk - 1) / chunk), n_tensors);
+  hipLaunchKernelGGL(multi_gather_acc_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const GatherDesc*)descs_dev, flat, chunk);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_zero_f32(float* x, long n, void* stream) {
+  MV_CHECK_ARG(x && n > 0 && ((uintptr_t)x & 15) == 0);      // 16-byte aligned: always the fill kernel, never a memset node
+  MV_HIP(mvi_zero_async(x, sizeof(float) * (size_t)n, (hipStream_t)stream));
+  return MV_OK;
+}
+
+static_assert(sizeof(double) * GN_GRID == MV_GRAD_NORM_WORKSPACE_BYTES, "header and kernel disagree on the partials' size");
+
+extern "C" int mv_grad_norm(const float* g, long n, float pre_scale, const float* max_norm_dev, float max_norm, void* workspace,
+                            float* out, void* stream) {
+  MV_CHECK_ARG(g && workspace && out && n > 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)workspace & 7) == 0);
+  MV_CHECK_ARG(max_norm_dev || max_norm > 0.f);
+  hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(GN_GRID), dim3(256), 0, (hipStream_t)stream, g, n, (double*)workspace);
+  MV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, GN_GRID, pre_scale,
+                     max_norm_dev, max_norm, out);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_adamw_flat_clip(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                  const float* coef_dev, void* stream) {
+  MV_CHECK_ARG(p && g && m && v && n > 0 && coef_dev && (step_dev || step >= 1));
+  float bc1 = 1.f, bc2 = 1.f;
+  if (!step_dev) { bc1 = 1.f - powf(beta1, (float)step); bc2 = 1.f - powf(beta2, (float)step); }
+  hipLaunchKernelGGL(adamw_clip_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hparams_dev,
+                     step_dev, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, coef_dev);
   MV_LAUNCH_CHECK();
   return MV_OK;
 }

@@ -108,11 +108,29 @@ class VocoderTrainer:
 
     fp32 training with the discriminators on the matrix cores: `vocoder.discriminators.set_fp32_operands("split")` with fp32
     activations runs both discriminator families on split-operand MFMA kernels (every operand hi + lo bf16, ~2^-16 relative) instead
-    of the generic fp32 kernels (the default "exact"); 16-bit activations are not affected."""
+    of the generic fp32 kernels (the default "exact"); 16-bit activations are not affected.
+
+    `accumulation_steps=N` (configs/train_config.yaml: gradient_accumulation_steps): a window is N consecutive `train_step` calls.
+    Every call runs the full forward / backward in the reference's order and adds its gradients to both optimizers' flat buffers
+    (zeroed by a kernel at the window's start); both optimizers step only on the window's last call, on the window's sum times 1/N.
+    The weights are constant inside a window, so the generator pass of every micro-step sees the discriminators of the window's
+    START (in the reference's single step it sees them just updated): the ordinary meaning of accumulation for a two-optimizer step.
+    The dropout stream advances on every call, the schedulers and the optimizers' step counts once per window; under data parallel
+    only the last call of a window reduces.  `max_grad_norm=x` (configs/incremental_train_config.yaml): each optimizer's gradient
+    - averaged over the window and over the ranks - is clipped to global L2 norm x before its update, like
+    torch.nn.utils.clip_grad_norm_ on that optimizer's parameters; the norm and the coefficient stay on the device
+    (`optimizer.grad_norm`; with `return_tensors=True` the stepping call also returns `generator_grad_norm` /
+    `discriminator_grad_norm`), and a captured step follows `optimizer.max_grad_norm` at every replay.  Both need FlatAdamW
+    optimizers.  With `use_graph` a window replays two graphs per input signature: "accumulate" and "accumulate + step".
+    `save_checkpoint` inside a window raises; `load_checkpoint` starts a new window."""
 
     def __init__(self, vocoder: ModifiedHiFiGANVocoder, generator_optimizer=None, discriminator_optimizer=None,
                  device=None, mel_mode: str = "stft", grad_sync=None, bucket_mib: int = 8, use_graph: bool = False,
-                 graph_warmup: int = 2, dropout_rng: Optional[str] = None, schedulers=()):
+                 graph_warmup: int = 2, dropout_rng: Optional[str] = None, schedulers=(), accumulation_steps: int = 1,
+                 max_grad_norm: Optional[float] = None):
+        from .optim import FlatAdamW, check_accumulation_args
+        self.accumulation_steps, self.max_grad_norm = check_accumulation_args("VocoderTrainer", accumulation_steps, max_grad_norm)
+        self._micro = 0                      # position of the next train_step call inside its accumulation window
         device = device or torch.device("cuda")
         self.vocoder = vocoder.to(device)
         self.device = device
@@ -120,6 +138,13 @@ class VocoderTrainer:
             generator_optimizer, discriminator_optimizer = self.default_optimizers(self.vocoder)
         self.generator_optimizer = generator_optimizer
         self.discriminator_optimizer = discriminator_optimizer
+        if self.accumulation_steps > 1 or self.max_grad_norm is not None:
+            for opt in (generator_optimizer, discriminator_optimizer):
+                if not isinstance(opt, FlatAdamW):
+                    raise ValueError("VocoderTrainer: accumulation_steps > 1 and max_grad_norm work on FlatAdamW's gradient arena; "
+                                     f"got a {type(opt).__name__}")
+                if self.max_grad_norm is not None:
+                    opt.max_grad_norm = self.max_grad_norm
         self.mel_mode = mel_mode
         if grad_sync is None:
             import torch.distributed as dist
@@ -158,28 +183,35 @@ class VocoderTrainer:
             ov = self._overlap[id(opt)] = OverlappedGradSync(opt, bucket_mib=self.bucket_mib)
         return ov
 
-    def _backward_and_step(self, loss, opt):
-        """loss.backward() + (data-parallel gradient mean) + optimizer step (complete_vocoder.py:217-218, :225-226)."""
+    def _backward_and_step(self, loss, opt, do_step=True, defer=False):
+        """loss.backward() + (data-parallel gradient mean) + optimizer step (complete_vocoder.py:217-218, :225-226).  Inside an
+        accumulation window the gathers add to the arena; `do_step` is False on every call of the window but the last: no
+        collective and no update then.  `defer`: everything but the update - the gradient scale for `_apply_step` is returned."""
         from .optim import FlatAdamW
         if isinstance(opt, FlatAdamW):
+            acc = self.accumulation_steps > 1
             ov = self.overlap_sync(opt)
             if ov is not None:
-                ov.begin()                          # buckets reduce while autograd is still producing the other gradients
+                if acc:
+                    ov.begin(accumulate=True, reduce=do_step)
+                else:
+                    ov.begin()                      # buckets reduce while autograd is still producing the other gradients
                 loss.backward()
                 scale = ov.finish()
             else:
                 loss.backward()
-                flat = opt.gather_grads()
+                flat = opt.gather_grads(accumulate=True) if acc else opt.gather_grads()
                 scale = 1.0
-                if self.grad_sync:
+                if self.grad_sync and do_step:
                     self.grad_sync.start(flat)
                     scale = self.grad_sync.finish()
-            opt.step(grad_scale=scale, gathered=True)
-            if not torch.cuda.is_current_stream_capturing():
-                from . import disc_fused
-                disc_fused._packs.refresh_owned(opt)     # all conv packs of the stepped module in one launch
-            # (captured step: each pack is recorded where the next forward misses its cache - the batched refresh would upload a new
-            #  pointer table from pageable memory, which a capture does not allow)
+            if not do_step:
+                return None
+            if acc:
+                scale = scale * (1.0 / self.accumulation_steps)
+            if defer:
+                return scale
+            self._apply_step(opt, scale)
         else:
             loss.backward()
             if self.grad_sync:
@@ -192,39 +224,67 @@ class VocoderTrainer:
                             p.grad.div_(w)
             opt.step()
 
+    def _apply_step(self, opt, scale):
+        """The FlatAdamW update from the gathered (and reduced) arena, clipped when the trainer has a max_grad_norm."""
+        if self.max_grad_norm is None:
+            opt.step(grad_scale=scale, gathered=True)
+        else:           # the optimizer's own value: it may be changed between steps (a captured step reads it at every replay)
+            opt.step(grad_scale=scale, gathered=True, max_grad_norm=opt.max_grad_norm)
+        if not torch.cuda.is_current_stream_capturing():
+            from . import disc_fused
+            disc_fused._packs.refresh_owned(opt)     # all conv packs of the stepped module in one launch
+        # (captured step: each pack is recorded where the next forward misses its cache - the batched refresh would upload a new
+        #  pointer table from pageable memory, which a capture does not allow)
+
     def train_step(self, mel_spectrogram, real_audio, speaker_embedding=None, emotion_embedding=None,
                    return_tensors: bool = False) -> Dict[str, float]:
         mel_spectrogram = mel_spectrogram.to(self.device)
         real_audio = real_audio.to(self.device)
+        n_acc, k = self.accumulation_steps, self._micro
+        do_step = k == n_acc - 1                   # (always, without accumulation)
+        if n_acc > 1 and k == 0:                   # a new window: both arenas start from zero, every micro-step adds
+            self.discriminator_optimizer.zero_arena()
+            self.generator_optimizer.zero_arena()
         if self.use_graph and self._graph_ok():
-            res = self._graph_step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
+            res = self._graph_step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step)
         else:
-            res = self._step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
-        for sch in self.schedulers:
-            sch.step()
-        return res if return_tensors else self.to_floats(res)       # complete_vocoder.py:229-233 returns .item() floats
+            res = self._step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step)
+        self._micro = (k + 1) % n_acc
+        if do_step:
+            for sch in self.schedulers:
+                sch.step()
+        if not return_tensors:
+            return self.to_floats(res)             # complete_vocoder.py:229-233 returns .item() floats
+        if do_step and self.max_grad_norm is not None:
+            res = dict(res, generator_grad_norm=self.generator_optimizer.grad_norm,
+                       discriminator_grad_norm=self.discriminator_optimizer.grad_norm)
+        return res
 
-    def _step(self, mel_spectrogram, real_audio, speaker_embedding, emotion_embedding):
+    def _step(self, mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step=True):
         """One step under the trainer's dropout stream; an eager step advances the stream by the masks it drew (a captured one leaves
         that to each replay)."""
         rng = self.dropout_rng
         if rng is None:
-            return self._step_body(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
+            return self._step_body(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step)
         rng.slots_used = 0
         with Fn.use_dropout_rng(rng):
-            out = self._step_body(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding)
+            out = self._step_body(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step)
         if not torch.cuda.is_current_stream_capturing():
             rng.advance()
         return out
 
-    def _step_body(self, mel_spectrogram, real_audio, speaker_embedding, emotion_embedding):
-        """One step in the reference's order (complete_vocoder.py:207-226); returns device tensors."""
+    def _step_body(self, mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step=True):
+        """One step in the reference's order (complete_vocoder.py:207-226); returns device tensors.  do_step=False (a micro-step
+        inside an accumulation window): the same passes, the gradients only accumulate."""
         out = self.vocoder(mel_spectrogram, speaker_embedding, emotion_embedding)
         fake_audio = out["generated_waveform"]
         # discriminator step on the detached fake
         self.discriminator_optimizer.zero_grad()
         d_losses = self.vocoder.compute_discriminator_losses(real_audio, fake_audio.detach())
-        self._backward_and_step(d_losses["total_loss"], self.discriminator_optimizer)
+        # (inside an accumulation window the weights are constant: the discriminators' update waits until the generator's gradients
+        #  of the window's last micro-step exist too)
+        defer = self.accumulation_steps > 1
+        d_scale = self._backward_and_step(d_losses["total_loss"], self.discriminator_optimizer, do_step, defer)
         # generator step: discriminators re-evaluated after their update; their own weight gradients are not needed
         # (the reference accumulates and then zeroes them at the next D step)
         self.generator_optimizer.zero_grad()
@@ -236,7 +296,10 @@ class VocoderTrainer:
                 g_losses = self.vocoder.compute_generator_losses(real_audio, fake_audio, target, None)
             else:   # the reference's placeholder: generated_mel = mel_spectrogram -> the term is zero
                 g_losses = self.vocoder.compute_generator_losses(real_audio, fake_audio, mel_spectrogram, mel_spectrogram)
-            self._backward_and_step(g_losses["total_loss"], self.generator_optimizer)
+            g_scale = self._backward_and_step(g_losses["total_loss"], self.generator_optimizer, do_step, defer)
+            if defer and do_step:
+                self._apply_step(self.discriminator_optimizer, d_scale)
+                self._apply_step(self.generator_optimizer, g_scale)
         finally:
             for p in self._d_params:
                 p.requires_grad_(True)
@@ -252,11 +315,14 @@ class VocoderTrainer:
         return single and not self.grad_sync and isinstance(self.generator_optimizer, FlatAdamW) and \
             isinstance(self.discriminator_optimizer, FlatAdamW)
 
-    def _graph_step(self, mel, real, spk, emo):
+    def _graph_step(self, mel, real, spk, emo, do_step=True):
         sig = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in (mel, real, spk, emo))
-        st = self._graphs.get(sig)
+        # one graph per (input signature, phase); with accumulation the phases are "accumulate" and "accumulate + step", each with its
+        # own warm-up steps; the optimizers' state (runs, state block, step counts) belongs to the stepping phase only
+        key = sig if self.accumulation_steps == 1 else sig + ("step" if do_step else "accumulate",)
+        st = self._graphs.get(key)
         if st is None:
-            st = self._graphs[sig] = {"warm": 0, "graph": None}
+            st = self._graphs[key] = {"warm": 0, "graph": None}
         # warm-up steps and the capture share ONE side stream: autograd pins every parameter's AccumulateGrad node to the stream it
         # was first used on, and a node pinned to the default stream would pull the capture back onto it (and invalidate it)
         if getattr(self, "_gstream", None) is None:
@@ -266,12 +332,12 @@ class VocoderTrainer:
             st["warm"] += 1                       # eager: packs weights, sets launch attributes, sizes every cache
             gs.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(gs):
-                out = self._step(mel, real, spk, emo)
+                out = self._step(mel, real, spk, emo, do_step)
             torch.cuda.current_stream().wait_stream(gs)
             return out
         gopt, dopt = self.generator_optimizer, self.discriminator_optimizer
         rng = self.dropout_rng
-        if st["graph"] is not None and not (gopt.runs_match(st["gstate"]) and dopt.runs_match(st["dstate"])):
+        if st["graph"] is not None and do_step and not (gopt.runs_match(st["gstate"]) and dopt.runs_match(st["dstate"])):
             # a restored optimizer state split or merged the runs of equal step count that this graph updates: recapture
             torch.cuda.synchronize()              # (its last replay may still be running on the pool it frees)
             st["graph"] = st["out"] = st["gstate"] = st["dstate"] = None
@@ -287,13 +353,13 @@ class VocoderTrainer:
             graph = torch.cuda.CUDAGraph()
             if os.environ.get("MV_GRAPH_DOT"):
                 graph.enable_debug_mode()
-            gopt.capture_begin()
-            dopt.capture_begin()
+            gopt.capture_begin(stepping=do_step)
+            dopt.capture_begin(stepping=do_step)
             if rng is not None:
                 rng.device_block(self.device)     # allocated before the capture: the graph keeps its address
             try:
                 with torch.cuda.graph(graph, stream=gs):
-                    st["out"] = self._step(*st["inputs"])
+                    st["out"] = self._step(*st["inputs"], do_step)
                 st["gstate"], st["dstate"] = gopt.capture_end(), dopt.capture_end()
                 st["dropout_slots"] = rng.slots_used if rng is not None else 0
             except Exception:
@@ -313,8 +379,9 @@ class VocoderTrainer:
         def replay():
             # the host's per-step state (step counts + 1, lr and the other AdamW inputs, the dropout stream's counter) -> the state
             # blocks the graph reads, on the replay's stream: a few hundred bytes, asynchronously
-            dopt.before_replay(st["dstate"])
-            gopt.before_replay(st["gstate"])
+            if do_step:
+                dopt.before_replay(st["dstate"])
+                gopt.before_replay(st["gstate"])
             if rng is not None:
                 rng.upload()
             st["graph"].replay()
@@ -323,8 +390,9 @@ class VocoderTrainer:
         with torch.cuda.stream(gs):
             replay()
         cur.wait_stream(gs)
-        dopt.after_replay(st["dstate"])
-        gopt.after_replay(st["gstate"])
+        if do_step:
+            dopt.after_replay(st["dstate"])
+            gopt.after_replay(st["gstate"])
         if rng is not None:
             rng.advance(st["dropout_slots"])
         return st["out"]
@@ -335,6 +403,10 @@ class VocoderTrainer:
         return {k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in losses.items()}
 
     def save_checkpoint(self, path: str):
+        if self._micro != 0:
+            raise RuntimeError(f"VocoderTrainer.save_checkpoint: in the middle of an accumulation window ({self._micro} of "
+                               f"{self.accumulation_steps} micro-steps taken): the partial gradient sums are not part of a checkpoint - "
+                               "save after the call that steps")
         ck = {"vocoder_state_dict": self.vocoder.state_dict(),
               # torch.optim.AdamW's layout, so the reference's own load path (complete_vocoder.py:463-468) reads the file too
               "generator_optimizer_state_dict": self.generator_optimizer.torch_state_dict(),
@@ -344,6 +416,9 @@ class VocoderTrainer:
             ck["dropout_rng_state"] = self.dropout_rng.state_dict()
         if self.schedulers:
             ck["scheduler_state_dicts"] = [s.state_dict() for s in self.schedulers]
+        if self.accumulation_steps > 1 or self.max_grad_norm is not None:
+            # informational (the constructor's arguments decide on load); a default trainer writes the keys it always wrote
+            ck["accumulation_steps"], ck["max_grad_norm"] = self.accumulation_steps, self.max_grad_norm
         torch.save(ck, path)
 
     def load_checkpoint(self, path: str):
@@ -355,3 +430,4 @@ class VocoderTrainer:
             self.dropout_rng.load_state_dict(ck["dropout_rng_state"])
         for sch, sd in zip(self.schedulers, ck.get("scheduler_state_dicts", ())):
             sch.load_state_dict(sd)
+        self._micro = 0                      # a checkpoint is always a window boundary

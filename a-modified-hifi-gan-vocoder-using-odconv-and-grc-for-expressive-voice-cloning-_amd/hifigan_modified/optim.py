@@ -49,6 +49,17 @@ class DeviceStateBlock:
         slot[1] = ev
 
 
+def check_accumulation_args(who, accumulation_steps, max_grad_norm):
+    """The trainers' two keywords (configs/train_config.yaml: gradient_accumulation_steps; configs/incremental_train_config.yaml:
+    max_grad_norm): a whole number of micro-steps >= 1 and a positive norm (or None: no clipping)."""
+    if isinstance(accumulation_steps, bool) or not isinstance(accumulation_steps, (int, np.integer)) or accumulation_steps < 1:
+        raise ValueError(f"{who}: accumulation_steps must be an integer >= 1, got {accumulation_steps!r}")
+    if max_grad_norm is not None and (isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float, np.floating))
+                                      or not max_grad_norm > 0):
+        raise ValueError(f"{who}: max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+    return int(accumulation_steps), (None if max_grad_norm is None else float(max_grad_norm))
+
+
 class FlatAdamW:
     def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, exclude=()):
         excl = {id(p) for p in exclude}
@@ -92,15 +103,39 @@ class FlatAdamW:
         self._descs["n"] = [p.numel() for p in self.params]
         self._max_len = int(self._descs["n"].max())
         self._has_grad = None        # per parameter, set by the gathers of the current step (None = every parameter)
+        # max_grad_norm clipping (step(max_grad_norm=...)): the value a captured step's replays read (before_replay uploads it) and the
+        # trainers pass; None = no clipping.  grad_norm: the last step's gradient norm, a 0-d device tensor (never read by the host here)
+        self.max_grad_norm = None
+        self.grad_norm = None
+        self._clip_buf = None        # fp32 {norm, coef} + the norm kernel's workspace, allocated at the first clipped step
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
             p.grad = None
 
-    def gather_grads(self):
-        """param.grad tensors (fresh per backward) -> flat fp32 buffer; missing grads contribute zeros."""
+    def zero_arena(self):
+        """Start of an accumulation window: the flat gradient buffer is zeroed (by a kernel, also inside a captured step) and no
+        parameter has a gradient yet; the gathers of the window then run with accumulate=True."""
+        from .torch_ops import OPS
+        OPS.zero_(self.flat_g)
+        self._has_grad = [False] * len(self.params)
+
+    def _gather(self, table, n, max_len, accumulate):
+        if accumulate:
+            from .torch_ops import OPS
+            OPS.multi_gather_acc_(table, n, max_len, self.flat_g)       # mv_multi_gather_acc
+        else:
+            N.call("mv_multi_gather", c_void_p(table.data_ptr()), n, max_len, c_void_p(self.flat_g.data_ptr()), ops._stream())
+
+    def gather_grads(self, accumulate=False):
+        """param.grad tensors (fresh per backward) -> flat fp32 buffer; missing grads contribute zeros.  accumulate=True adds to the
+        buffer instead (micro-steps of an accumulation window): a missing grad then adds nothing, and a parameter counts as having a
+        gradient when any gather since the last overwrite / zero_arena() gave it one."""
         d = self._descs
-        self._has_grad = [p.grad is not None for p in self.params]
+        has = [p.grad is not None for p in self.params]
+        if accumulate and self._has_grad is not None:
+            has = [a or b for a, b in zip(self._has_grad, has)]
+        self._has_grad = has
         for i, p in enumerate(self.params):
             g = p.grad
             if g is None:
@@ -111,8 +146,7 @@ class FlatAdamW:
                     p.grad = g
                 d["src"][i], d["dtype"][i] = g.data_ptr(), ops._DT[g.dtype]
         table = self._upload(d)
-        N.call("mv_multi_gather", c_void_p(table.data_ptr()), len(self.params), self._max_len,
-               c_void_p(self.flat_g.data_ptr()), ops._stream())
+        self._gather(table, len(self.params), self._max_len, accumulate)
         self._table = table   # keep alive until the launch has consumed it
         return self.flat_g
 
@@ -153,15 +187,16 @@ class FlatAdamW:
         slot[1] = ev
         return dev
 
-    def gather_range(self, i0, i1):
+    def gather_range(self, i0, i1, accumulate=False):
         """Gather the gradients of parameters i0..i1-1 only (one launch): the per-bucket form used by
-        parallel.OverlappedGradSync while the backward is still running.  Missing gradients contribute zeros."""
+        parallel.OverlappedGradSync while the backward is still running.  Missing gradients contribute zeros; accumulate=True adds
+        to the buffer like gather_grads(accumulate=True)."""
         d = self._descs[i0:i1].copy()
         if self._has_grad is None or len(self._has_grad) != len(self.params):
             self._has_grad = [True] * len(self.params)
         for j, p in enumerate(self.params[i0:i1]):
             g = p.grad
-            self._has_grad[i0 + j] = g is not None
+            self._has_grad[i0 + j] = (g is not None) or (accumulate and self._has_grad[i0 + j])
             if g is None:
                 d["src"][j], d["dtype"][j] = 0, 0
             else:
@@ -170,11 +205,24 @@ class FlatAdamW:
                     p.grad = g
                 d["src"][j], d["dtype"][j] = g.data_ptr(), ops._DT[g.dtype]
         table = self._upload(d)
-        N.call("mv_multi_gather", c_void_p(table.data_ptr()), i1 - i0, int(d["n"].max()),
-               c_void_p(self.flat_g.data_ptr()), ops._stream())
+        self._gather(table, i1 - i0, int(d["n"].max()), accumulate)
         self._tables = getattr(self, "_tables", [])[-64:] + [table]   # keep alive until the launches have consumed them
 
-    def step(self, grad_scale=1.0, gathered=False):
+    def _clip_slots(self):
+        """fp32 device buffer: [0] the gradient norm, [1] the clip coefficient, then the norm kernel's workspace."""
+        if self._clip_buf is None:
+            from .torch_ops import GRAD_NORM_WS_WORDS
+            self._clip_buf = torch.zeros(2 + GRAD_NORM_WS_WORDS, device=self.flat_p.device, dtype=torch.float32)
+            self.grad_norm = self._clip_buf[0]
+        return self._clip_buf
+
+    def step(self, grad_scale=1.0, gathered=False, max_grad_norm=None):
+        """One AdamW update from the flat gradient buffer times grad_scale (1/world x 1/accumulation steps).  max_grad_norm: clip the
+        scaled gradient's global L2 norm to it first (torch.nn.utils.clip_grad_norm_ over this optimizer's parameters): ONE norm over
+        the whole arena - parameters without a gradient hold zeros there - whose coefficient every run of the update multiplies in on
+        the device; `self.grad_norm` is that norm as a device tensor.  None: no norm, the unclipped kernels."""
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"FlatAdamW.step: max_grad_norm must be positive, got {max_grad_norm}")
         if not gathered:
             self.gather_grads()
         # torch.optim.AdamW leaves a parameter whose .grad is None untouched (no weight decay, no moment decay, no step): update only
@@ -193,12 +241,25 @@ class FlatAdamW:
                 i += 1
         from .torch_ops import OPS
         cap = self._capture
+        clip = None
+        if max_grad_norm is not None:
+            clip = self._clip_slots() if cap is None else self._clip_buf
+            if cap is None:
+                OPS.grad_norm(self.flat_g, clip, None, float(max_grad_norm), float(grad_scale))
+            else:           # captured: max_norm is word 5 of the state block, refreshed from self.max_grad_norm before every replay
+                if self.max_grad_norm is None or self._clip_buf is None:
+                    raise RuntimeError("FlatAdamW: set optimizer.max_grad_norm before capture_begin() of a step that clips")
+                cap["clip"] = True
+                OPS.grad_norm(self.flat_g, clip, cap["block"].dev.view(torch.float32)[5:6], 0.0, float(grad_scale))
         for (i0, i1, off, cnt) in runs:   # torch.ops.mi355x_vocoder.fused_adamw_ (in place on the arena slices; mv_adamw_flat)
             t = self.steps[i0] + 1
             args = (self.flat_p[off:off + cnt], self.flat_g[off:off + cnt], self.exp_avg[off:off + cnt], self.exp_avg_sq[off:off + cnt],
                     float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay))
             if cap is None:
-                OPS.fused_adamw_(*args, int(t), float(grad_scale))
+                if clip is None:
+                    OPS.fused_adamw_(*args, int(t), float(grad_scale))
+                else:
+                    OPS.fused_adamw_clip_(*args[:4], None, None, *args[4:], int(t), float(grad_scale), clip[1:2])
                 for k in range(i0, i1):
                     self.steps[k] = t
             else:
@@ -208,7 +269,11 @@ class FlatAdamW:
                 if r >= len(cap["planned"]):
                     raise RuntimeError("FlatAdamW: the captured step does not update the arena as one run per step count")
                 blk = cap["block"].dev
-                OPS.fused_adamw_hp_(*args[:4], blk.view(torch.float32)[:5], blk.view(torch.int32)[8 + r:9 + r], float(grad_scale))
+                if clip is None:
+                    OPS.fused_adamw_hp_(*args[:4], blk.view(torch.float32)[:5], blk.view(torch.int32)[8 + r:9 + r], float(grad_scale))
+                else:
+                    OPS.fused_adamw_clip_(*args[:4], blk.view(torch.float32)[:5], blk.view(torch.int32)[8 + r:9 + r], 0.0, 0.0, 0.0, 0.0,
+                                          0.0, 0, float(grad_scale), clip[1:2])
                 cap["runs"].append((i0, i1))
         self.step_count = max(self.steps)
         self._has_grad = None
@@ -216,16 +281,22 @@ class FlatAdamW:
         self._refresh_shadows()
 
     # ---- captured training steps (VocoderTrainer / HiFiGANTrainer with use_graph): everything the step launches is recorded once
-    def capture_begin(self):
+    def capture_begin(self, stepping=True):
         """Call right before a training step is captured into a HIP graph (torch.cuda.graph): the gathers' descriptor tables become
         pinned and persistent, and AdamW reads its hyper-parameters and per-run step counts from a device state block (int32 words:
-        0-4 fp32 {lr, beta1, beta2, eps, weight_decay}, 8 + r the count of run r) that before_replay() refreshes."""
+        0-4 fp32 {lr, beta1, beta2, eps, weight_decay}, 5 fp32 max_grad_norm (read by the gradient norm of a clipped step, 0 otherwise),
+        6-7 unused, 8 + r the count of run r) that before_replay() refreshes.  The norm and the clip coefficient themselves are
+        written by the device into a buffer of their own (allocated here, before the capture).  stepping=False: the captured body
+        only gathers (a micro-step inside an accumulation window) - no update, no runs, nothing to refresh."""
         dev = self.flat_p.device
-        planned = self._planned_runs()
+        planned = self._planned_runs() if stepping else []
         block = DeviceStateBlock(4 * (8 + len(planned)), dev)
         nbytes = self._descs.nbytes
         pinned = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(4)]
-        self._capture = {"keep": [], "block": block, "runs": [], "planned": planned, "pinned": pinned}
+        if self.max_grad_norm is not None:
+            self._clip_slots()
+        self._capture = {"keep": [], "block": block, "runs": [], "planned": planned, "pinned": pinned, "clip": False,
+                         "stepping": stepping}
 
     def _planned_runs(self):
         """Runs of equal step count over ALL parameters (a captured step must give every parameter of the arena a gradient)."""
@@ -245,7 +316,7 @@ class FlatAdamW:
         if cap["runs"] != cap["planned"]:
             raise RuntimeError("FlatAdamW: the captured step left parameters without a gradient: a captured step must update every "
                                "parameter of the arena")
-        return {"keep": cap["keep"], "block": cap["block"], "runs": cap["runs"]}
+        return {"keep": cap["keep"], "block": cap["block"], "runs": cap["runs"], "clip": cap["clip"], "stepping": cap["stepping"]}
 
     def runs_match(self, state):
         """True while the host's step counts still form the runs the captured step was recorded with (a restored state can split or
@@ -259,6 +330,10 @@ class FlatAdamW:
             raise RuntimeError("FlatAdamW: the step counts no longer form the captured runs: recapture the step")
         words = np.zeros(8 + len(state["runs"]), dtype=np.int32)
         words[:5].view(np.float32)[:] = (self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
+        if state.get("clip"):
+            if self.max_grad_norm is None or not self.max_grad_norm > 0:
+                raise RuntimeError("FlatAdamW: the captured step clips its gradient norm: max_grad_norm must stay a positive number")
+            words[5:6].view(np.float32)[:] = self.max_grad_norm
         words[8:] = [self.steps[i0] + 1 for (i0, _) in state["runs"]]
         state["block"].upload(words)
 

@@ -58,6 +58,7 @@ class GradSynchronizer:
     def __init__(self, bucket_mib=32):
         self.bucket_elems = bucket_mib * (1 << 20) // 4
         self.pending = []
+        self.collectives = 0          # all-reduces issued so far
 
     @property
     def world(self):
@@ -68,6 +69,7 @@ class GradSynchronizer:
             return
         for o, n in bucket_ranges(flat_grad.numel(), self.bucket_elems):
             self.pending.append(dist.all_reduce(flat_grad[o:o + n], op=dist.ReduceOp.SUM, async_op=True))
+            self.collectives += 1
 
     def finish(self):
         for w in self.pending:
@@ -82,7 +84,10 @@ class OverlappedGradSync:
     usage per step:   sync.begin(); loss.backward(); scale = sync.finish(); opt.step(grad_scale=scale, gathered=True)
     `finish()` gathers and reduces whatever did not complete during the backward (parameters without a gradient count as
     zeros, exactly like FlatAdamW.gather_grads), waits for every bucket and returns 1/world.  With world size 1 it degrades to
-    one gather.  `exposed_ms` accumulates the time the compute stream spent waiting in finish() (what the overlap did not hide)."""
+    one gather.  `exposed_ms` accumulates the time the compute stream spent waiting in finish() (what the overlap did not hide).
+
+    Gradient accumulation: `begin(accumulate=True)` makes the bucket gathers ADD to the flat buffer, `begin(reduce=False)` gathers
+    without any collective - the micro-steps before the last of a window; the last one accumulates and reduces the window's sum."""
 
     def __init__(self, opt, bucket_mib=8, timing=False):
         self.opt = opt
@@ -110,6 +115,8 @@ class OverlappedGradSync:
         self.timing = timing
         self.exposed_ms = 0.0
         self.reduced_bytes = 0
+        self.collectives = 0          # all-reduces issued so far
+        self._accumulate, self._reduce = False, True
         self._ev = []
         for i, p in enumerate(opt.params):
             p.register_post_accumulate_grad_hook(self._make_hook(i))
@@ -135,8 +142,9 @@ class OverlappedGradSync:
                 self._next -= 1
         return hook
 
-    def begin(self):
+    def begin(self, accumulate=False, reduce=True):
         """Arm the hooks for the next backward of this parameter group."""
+        self._accumulate, self._reduce = accumulate, reduce
         self._have = [0] * len(self.buckets)
         self._launched = [False] * len(self.buckets)
         self._next = len(self.buckets) - 1
@@ -145,9 +153,13 @@ class OverlappedGradSync:
 
     def _launch(self, b):
         a, e, off, n = self.buckets[b]
-        self.opt.gather_range(a, e)
+        if self._accumulate:
+            self.opt.gather_range(a, e, accumulate=True)
+        else:
+            self.opt.gather_range(a, e)
         self._launched[b] = True
-        if self.world > 1:
+        if self.world > 1 and self._reduce:
+            self.collectives += 1
             self._works.append(dist.all_reduce(self.opt.flat_g[off:off + n], op=dist.ReduceOp.SUM, async_op=True))
             self.reduced_bytes += 4 * n
 

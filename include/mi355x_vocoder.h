@@ -362,6 +362,28 @@ int mv_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, floa
  * Same arithmetic as mv_adamw_flat_dev: a captured training step reads what the host uploaded before the replay. */
 int mv_adamw_flat_hp(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
                      float grad_scale, void* stream);
+/* Gradient accumulation and max_grad_norm clipping on the arena (configs/train_config.yaml: gradient_accumulation_steps;
+ * configs/incremental_train_config.yaml: max_grad_norm 1.0 = torch.nn.utils.clip_grad_norm_, norm_type 2).
+ *   mv_multi_gather_acc: mv_multi_gather's table and grid, flat[dst_off + i] += src[i] (src == NULL adds nothing).  Neither gather
+ *     writes the padding words between parameters: they stay zero from the arena's allocation on.
+ *   mv_zero_f32: zero fill by a kernel launch (x 16-byte aligned): the start of an accumulation window, also inside a captured step.
+ *   mv_grad_norm: out[0] = norm = |pre_scale| * sqrt(sum g[i]^2), out[1] = coef = min(1, max_norm / (norm + 1e-6)); a non-finite
+ *     norm gives torch's coefficient (NaN -> NaN, inf -> 0).  g 16-byte aligned; workspace: MV_GRAD_NORM_WORKSPACE_BYTES of device
+ *     memory, 8-byte aligned; max_norm_dev (device fp32, optional) overrides max_norm.  Two launches (a fixed grid's per-workgroup
+ *     partials, then one workgroup), no atomics: the same input gives the same bits.  pre_scale is the factor AdamW applies to g
+ *     (1/accumulation steps x 1/world), so the norm is the averaged gradient's.
+ *   mv_adamw_flat_clip: AdamW with g multiplied by grad_scale * coef_dev[0].  hparams_dev / step_dev as in mv_adamw_flat_hp, each
+ *     optional: NULL takes the by-value arguments instead (mv_adamw_flat's arithmetic).  With a coefficient of exactly 1 the update
+ *     has the bits of the unclipped entry point of the same form. */
+#define MV_GRAD_NORM_WORKSPACE_BYTES 8192
+int mv_multi_gather_acc(const void* descs_dev, int n_tensors, long max_len, float* flat, void* stream);
+int mv_zero_f32(float* x, long n, void* stream);
+int mv_grad_norm(const float* g, long n, float pre_scale, const float* max_norm_dev, float max_norm, void* workspace, float* out,
+                 void* stream);
+int mv_adamw_flat_clip(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, const float* coef_dev,
+                       void* stream);
+
 /* uint8 keep-mask of nn.Dropout(p) (grc_lora.py:151,162): mask[i] = 1 with probability 1-p, Philox4x32-10 keyed by `seed`,
  * counter = element index / 8 (16 random bits per element; resolution 2^-16 on p). */
 int mv_dropout_mask(uint8_t* mask, long n, float p, long seed, void* stream);

@@ -191,65 +191,51 @@ __global__ __launch_bounds__(256) void scale_to_kernel(const T* __restrict__ x, 
 }
 
 // ------------------------------------------------------------------------------------------- AdamW on a flat fp32 arena
+// one element of torch.optim.AdamW: decoupled weight decay, the two moments, the bias-corrected step
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float wd,
+                                             float bc1, float bc2, float gscale) {
+  const float gr = g * gscale;
+  float pi = p * (1.f - lr * wd);                      // decoupled weight decay (torch.optim.AdamW)
+  const float mi = b1 * m + (1.f - b1) * gr;
+  const float vi = b2 * v + (1.f - b2) * gr * gr;
+  m = mi; v = vi;
+  const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+  pi -= (lr / bc1) * (mi / denom);
+  p = pi;
+}
+
+// The one AdamW kernel.  Every per-step input comes either by value or from device memory, each device pointer optional:
+//   hp   {lr, beta1, beta2, eps, weight_decay} (fp32) - the host refreshes them before each replay of a captured step, so schedules,
+//        lr changes and restored counts reach the graph; NULL: the by-value arguments
+//   step the step count (int32, already incremented: a captured HIP graph must not bake the host's count into its launch arguments),
+//        the bias corrections are then formed here; NULL: bc1 / bc2 as the host formed them
+//   coef the clip coefficient (the device slot grad_norm_finish_kernel wrote): g is multiplied by gscale * coef[0]; NULL: by gscale
+//        alone.  gscale * 1.0f is gscale, so with a coefficient of exactly 1 the update has the bits of the unclipped form.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
-                                                    float wd, float bc1, float bc2, float gscale) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gr = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);                 // decoupled weight decay (torch.optim.AdamW)
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    p[i] = pi;
+                                                    float* __restrict__ v, long n, const float* __restrict__ hp,
+                                                    const int* __restrict__ step, float lr, float b1, float b2, float eps, float wd,
+                                                    float bc1, float bc2, float gscale_, const float* __restrict__ coef) {
+  if (hp) { lr = hp[0]; b1 = hp[1]; b2 = hp[2]; eps = hp[3]; wd = hp[4]; }
+  if (step) {
+    const float t = (float)(*step);
+    bc1 = 1.f - powf(b1, t); bc2 = 1.f - powf(b2, t);
   }
+  const float gscale = coef ? gscale_ * coef[0] : gscale_;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    adamw_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2, gscale);
 }
 
-// the same with the step count read from device memory (a captured HIP graph must not bake the host's count into its launch arguments)
-__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
-                                                        float wd, const int* __restrict__ step, float gscale) {
-  const float t = (float)(*step);
-  const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gr = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    p[i] = pi;
-  }
-}
-
-// the same with every per-step input in device memory: {lr, beta1, beta2, eps, weight_decay} (fp32) and the step count (int32) - the
-// host refreshes them before each replay of a captured step, so schedules, lr changes and restored counts reach the graph
-__global__ __launch_bounds__(256) void adamw_hp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, long n, const float* __restrict__ hp,
-                                                       const int* __restrict__ step, float gscale) {
-  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4];
-  const float t = (float)(*step);
-  const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gr = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    p[i] = pi;
-  }
-}
-
-// gather many gradient tensors (any storage type, given per tensor) into one flat fp32 buffer
+// gather many gradient tensors (any storage type, given per tensor) into one flat fp32 buffer: flat[dst_off + i] = src[i], a NULL
+// source writes zeros.  ACC, the accumulating form (gradient accumulation: micro-steps 2..N of a window): flat[dst_off + i] += src[i],
+// one fp32 add per element; a NULL source adds nothing (the block returns before touching memory).  Neither form touches the padding
+// words between parameters, which therefore stay zero from the arena's allocation on (grad_norm_partial_kernel reads them as part
+// of its slice).
 struct GatherDesc { const void* src; long dst_off; long n; int dtype; int pad; };
+template <bool ACC>
 __global__ __launch_bounds__(256) void multi_gather_kernel(const GatherDesc* __restrict__ descs, float* __restrict__ flat, int chunk) {
   const GatherDesc d = descs[blockIdx.y];
   const long beg = (long)blockIdx.x * chunk;
-  if (beg >= d.n) return;
+  if ((ACC && d.src == nullptr) || beg >= d.n) return;
   const long end = beg + chunk < d.n ? beg + chunk : d.n;
   for (long i = beg + threadIdx.x; i < end; i += blockDim.x) {
     float v;
@@ -257,24 +243,8 @@ __global__ __launch_bounds__(256) void multi_gather_kernel(const GatherDesc* __r
     else if (d.dtype == MV_F32) v = ((const float*)d.src)[i];
     else if (d.dtype == MV_BF16) v = ld<bf16>((const bf16*)d.src + i);
     else v = ld<f16>((const f16*)d.src + i);
-    flat[d.dst_off + i] = v;
-  }
-}
-
-// the accumulating form (gradient accumulation: micro-steps 2..N of a window): flat[dst_off + i] += src[i], one fp32 add per element.
-// A NULL source adds nothing; like the gather above it never touches the padding words between parameters, which therefore stay zero
-// from the arena's allocation on (grad_norm_partial_kernel reads them as part of its slice).
-__global__ __launch_bounds__(256) void multi_gather_acc_kernel(const GatherDesc* __restrict__ descs, float* __restrict__ flat, int chunk) {
-  const GatherDesc d = descs[blockIdx.y];
-  const long beg = (long)blockIdx.x * chunk;
-  if (d.src == nullptr || beg >= d.n) return;
-  const long end = beg + chunk < d.n ? beg + chunk : d.n;
-  for (long i = beg + threadIdx.x; i < end; i += blockDim.x) {
-    float v;
-    if (d.dtype == MV_F32) v = ((const float*)d.src)[i];
-    else if (d.dtype == MV_BF16) v = ld<bf16>((const bf16*)d.src + i);
-    else v = ld<f16>((const f16*)d.src + i);
-    flat[d.dst_off + i] += v;
+    if (ACC) flat[d.dst_off + i] += v;
+    else flat[d.dst_off + i] = v;
   }
 }
 
@@ -336,34 +306,6 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
     const float c = mx / (norm + 1e-6f);
     out[0] = norm;
     out[1] = c > 1.f ? 1.f : c;          // (a NaN norm stays a NaN coefficient, an infinite one gives 0: torch.clamp(max=1))
-  }
-}
-
-// ------------------------------------------------------------------------------------------- AdamW with the clip coefficient
-// adamw_kernel / adamw_hp_kernel with g multiplied by gscale * coef[0] (coef: the device slot grad_norm_finish_kernel wrote).  Every
-// per-step input comes either by value (the eager step: bias corrections formed on the host like mv_adamw_flat's) or from device
-// memory (the captured step: hp / step like mv_adamw_flat_hp's).  gscale * 1.0f is gscale, so with a coefficient of exactly 1 the
-// update has the bits of the unclipped kernel of the same form.
-__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, long n, const float* __restrict__ hp,
-                                                         const int* __restrict__ step, float lr, float b1, float b2, float eps,
-                                                         float wd, float bc1, float bc2, float gscale_,
-                                                         const float* __restrict__ coef) {
-  if (hp) { lr = hp[0]; b1 = hp[1]; b2 = hp[2]; eps = hp[3]; wd = hp[4]; }
-  if (step) {
-    const float t = (float)(*step);
-    bc1 = 1.f - powf(b1, t); bc2 = 1.f - powf(b2, t);
-  }
-  const float gscale = gscale_ * coef[0];
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gr = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    p[i] = pi;
   }
 }
 
@@ -596,50 +538,59 @@ extern "C" int mv_scale_to(const void* x, void* y, const float* factor_dev, floa
   return MV_OK;
 }
 
+// The one AdamW launch.  step_dev NULL: the bias corrections are formed here from `step`, like torch's host-side ones.
+static int adamw_launch(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, const float* coef_dev,
+                        void* stream) {
+  float bc1 = 1.f, bc2 = 1.f;
+  if (!step_dev) { bc1 = 1.f - powf(beta1, (float)step); bc2 = 1.f - powf(beta2, (float)step); }
+  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hparams_dev,
+                     step_dev, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, coef_dev);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
 extern "C" int mv_adamw_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                              float eps, float weight_decay, int step, float grad_scale, void* stream) {
   MV_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
-  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, weight_decay, bc1, bc2, grad_scale);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  return adamw_launch(p, g, m, v, n, nullptr, nullptr, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, stream);
 }
 
 extern "C" int mv_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                                  float eps, float weight_decay, const int* step_dev, float grad_scale, void* stream) {
   MV_CHECK_ARG(p && g && m && v && n > 0 && step_dev);
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, weight_decay, step_dev, grad_scale);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  return adamw_launch(p, g, m, v, n, nullptr, step_dev, lr, beta1, beta2, eps, weight_decay, 0, grad_scale, nullptr, stream);
 }
 
 extern "C" int mv_adamw_flat_hp(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
                                 float grad_scale, void* stream) {
   MV_CHECK_ARG(p && g && m && v && n > 0 && hparams_dev && step_dev);
-  hipLaunchKernelGGL(adamw_hp_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hparams_dev,
-                     step_dev, grad_scale);
+  return adamw_launch(p, g, m, v, n, hparams_dev, step_dev, 0.f, 0.f, 0.f, 0.f, 0.f, 0, grad_scale, nullptr, stream);
+}
+
+extern "C" int mv_adamw_flat_clip(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                  const float* coef_dev, void* stream) {
+  MV_CHECK_ARG(p && g && m && v && n > 0 && coef_dev && (step_dev || step >= 1));
+  return adamw_launch(p, g, m, v, n, hparams_dev, step_dev, lr, beta1, beta2, eps, weight_decay, step, grad_scale, coef_dev, stream);
+}
+
+template <bool ACC>
+static int gather_launch(const void* descs_dev, int n_tensors, long max_len, float* flat, void* stream) {
+  MV_CHECK_ARG(descs_dev && flat && n_tensors > 0 && n_tensors <= 65535 && max_len > 0);
+  const int chunk = 16384;
+  dim3 grid((unsigned)((max_len + chunk - 1) / chunk), n_tensors);
+  hipLaunchKernelGGL(multi_gather_kernel<ACC>, grid, dim3(256), 0, (hipStream_t)stream, (const GatherDesc*)descs_dev, flat, chunk);
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
 
 extern "C" int mv_multi_gather(const void* descs_dev, int n_tensors, long max_len, float* flat, void* stream) {
-  MV_CHECK_ARG(descs_dev && flat && n_tensors > 0 && n_tensors <= 65535 && max_len > 0);
-  const int chunk = 16384;
-  dim3 grid((unsigned)((max_len + chunk - 1) / chunk), n_tensors);
-  hipLaunchKernelGGL(multi_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const GatherDesc*)descs_dev, flat, chunk);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  return gather_launch<false>(descs_dev, n_tensors, max_len, flat, stream);
 }
 
 extern "C" int mv_multi_gather_acc(const void* descs_dev, int n_tensors, long max_len, float* flat, void* stream) {
-  MV_CHECK_ARG(descs_dev && flat && n_tensors > 0 && n_tensors <= 65535 && max_len > 0);
-  const int chunk = 16384;
-  dim3 grid((unsigned)((max_len + chunk - 1) / chunk), n_tensors);
-  hipLaunchKernelGGL(multi_gather_acc_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const GatherDesc*)descs_dev, flat, chunk);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  return gather_launch<true>(descs_dev, n_tensors, max_len, flat, stream);
 }
 
 extern "C" int mv_zero_f32(float* x, long n, void* stream) {
@@ -658,18 +609,6 @@ extern "C" int mv_grad_norm(const float* g, long n, float pre_scale, const float
   MV_LAUNCH_CHECK();
   hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, GN_GRID, pre_scale,
                      max_norm_dev, max_norm, out);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
-}
-
-extern "C" int mv_adamw_flat_clip(float* p, const float* g, float* m, float* v, long n, const float* hparams_dev, const int* step_dev,
-                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
-                                  const float* coef_dev, void* stream) {
-  MV_CHECK_ARG(p && g && m && v && n > 0 && coef_dev && (step_dev || step >= 1));
-  float bc1 = 1.f, bc2 = 1.f;
-  if (!step_dev) { bc1 = 1.f - powf(beta1, (float)step); bc2 = 1.f - powf(beta2, (float)step); }
-  hipLaunchKernelGGL(adamw_clip_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hparams_dev,
-                     step_dev, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, coef_dev);
   MV_LAUNCH_CHECK();
   return MV_OK;
 }

@@ -128,9 +128,10 @@ class VocoderTrainer:
                  device=None, mel_mode: str = "stft", grad_sync=None, bucket_mib: int = 8, use_graph: bool = False,
                  graph_warmup: int = 2, dropout_rng: Optional[str] = None, schedulers=(), accumulation_steps: int = 1,
                  max_grad_norm: Optional[float] = None):
-        from .optim import FlatAdamW, check_accumulation_args
-        self.accumulation_steps, self.max_grad_norm = check_accumulation_args("VocoderTrainer", accumulation_steps, max_grad_norm)
-        self._micro = 0                      # position of the next train_step call inside its accumulation window
+        from .training import GradWindow
+        self.window = w = GradWindow("VocoderTrainer", accumulation_steps, max_grad_norm, grad_sync, bucket_mib)
+        self.accumulation_steps, self.max_grad_norm = w.accumulation_steps, w.max_grad_norm
+        self.grad_sync, self.bucket_mib, self._overlap = w.grad_sync, w.bucket_mib, w.overlap
         device = device or torch.device("cuda")
         self.vocoder = vocoder.to(device)
         self.device = device
@@ -138,27 +139,17 @@ class VocoderTrainer:
             generator_optimizer, discriminator_optimizer = self.default_optimizers(self.vocoder)
         self.generator_optimizer = generator_optimizer
         self.discriminator_optimizer = discriminator_optimizer
-        if self.accumulation_steps > 1 or self.max_grad_norm is not None:
-            for opt in (generator_optimizer, discriminator_optimizer):
-                if not isinstance(opt, FlatAdamW):
-                    raise ValueError("VocoderTrainer: accumulation_steps > 1 and max_grad_norm work on FlatAdamW's gradient arena; "
-                                     f"got a {type(opt).__name__}")
-                if self.max_grad_norm is not None:
-                    opt.max_grad_norm = self.max_grad_norm
+        w.adopt(generator_optimizer, discriminator_optimizer)
         self.mel_mode = mel_mode
-        if grad_sync is None:
-            import torch.distributed as dist
-            grad_sync = "overlap" if (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1) else False
-        self.grad_sync = grad_sync
-        self.bucket_mib = bucket_mib
-        self._overlap = {}
         self._d_params = list(self.vocoder.discriminators.parameters())
         # use_graph: after `graph_warmup` eager steps at a given input signature the whole step (G forward, D step, G step, both
         # AdamW launches, every weight re-pack) is captured into ONE HIP graph and replayed: the step is ~1000 launches, more than
         # half of them shorter than the ~5 us it takes to issue one (single process, FlatAdamW optimizers only; static shapes)
         self.use_graph = use_graph
         self.graph_warmup = graph_warmup
-        self._graphs = {}
+        self._graphs = {}                    # (input signature[, phase]) -> the captured step's state (_graph_step)
+        self._gstream = None                 # the side stream of warm-up, capture and replay (created with the first captured step)
+        self.last_losses = None              # (generator, discriminator) loss dicts of the last eager step
         dropout_rng = dropout_rng or ("counter" if use_graph else "torch")
         if dropout_rng not in ("torch", "counter"):
             raise ValueError(f"VocoderTrainer: dropout_rng must be 'torch' or 'counter', got {dropout_rng!r}")
@@ -173,63 +164,17 @@ class VocoderTrainer:
         d = FlatAdamW(vocoder.discriminators.parameters(), lr=lr, betas=betas, weight_decay=weight_decay)
         return g, d
 
+    @property
+    def _micro(self):
+        return self.window.position
+
     def overlap_sync(self, opt):
         """The OverlappedGradSync of a FlatAdamW optimizer (created on first use), or None when overlap is off."""
-        if self.grad_sync != "overlap" and self.grad_sync is not True:
-            return None
-        ov = self._overlap.get(id(opt))
-        if ov is None:
-            from .parallel import OverlappedGradSync
-            ov = self._overlap[id(opt)] = OverlappedGradSync(opt, bucket_mib=self.bucket_mib)
-        return ov
-
-    def _backward_and_step(self, loss, opt, do_step=True, defer=False):
-        """loss.backward() + (data-parallel gradient mean) + optimizer step (complete_vocoder.py:217-218, :225-226).  Inside an
-        accumulation window the gathers add to the arena; `do_step` is False on every call of the window but the last: no
-        collective and no update then.  `defer`: everything but the update - the gradient scale for `_apply_step` is returned."""
-        from .optim import FlatAdamW
-        if isinstance(opt, FlatAdamW):
-            acc = self.accumulation_steps > 1
-            ov = self.overlap_sync(opt)
-            if ov is not None:
-                if acc:
-                    ov.begin(accumulate=True, reduce=do_step)
-                else:
-                    ov.begin()                      # buckets reduce while autograd is still producing the other gradients
-                loss.backward()
-                scale = ov.finish()
-            else:
-                loss.backward()
-                flat = opt.gather_grads(accumulate=True) if acc else opt.gather_grads()
-                scale = 1.0
-                if self.grad_sync and do_step:
-                    self.grad_sync.start(flat)
-                    scale = self.grad_sync.finish()
-            if not do_step:
-                return None
-            if acc:
-                scale = scale * (1.0 / self.accumulation_steps)
-            if defer:
-                return scale
-            self._apply_step(opt, scale)
-        else:
-            loss.backward()
-            if self.grad_sync:
-                import torch.distributed as dist
-                w = dist.get_world_size()
-                for g in opt.param_groups:
-                    for p in g["params"]:
-                        if p.grad is not None:
-                            dist.all_reduce(p.grad)
-                            p.grad.div_(w)
-            opt.step()
+        return self.window.overlap_sync(opt)
 
     def _apply_step(self, opt, scale):
-        """The FlatAdamW update from the gathered (and reduced) arena, clipped when the trainer has a max_grad_norm."""
-        if self.max_grad_norm is None:
-            opt.step(grad_scale=scale, gathered=True)
-        else:           # the optimizer's own value: it may be changed between steps (a captured step reads it at every replay)
-            opt.step(grad_scale=scale, gathered=True, max_grad_norm=opt.max_grad_norm)
+        """The (clipped) FlatAdamW update, then the stepped module's conv packs."""
+        self.window.apply(opt, scale)
         if not torch.cuda.is_current_stream_capturing():
             from . import disc_fused
             disc_fused._packs.refresh_owned(opt)     # all conv packs of the stepped module in one launch
@@ -240,16 +185,13 @@ class VocoderTrainer:
                    return_tensors: bool = False) -> Dict[str, float]:
         mel_spectrogram = mel_spectrogram.to(self.device)
         real_audio = real_audio.to(self.device)
-        n_acc, k = self.accumulation_steps, self._micro
-        do_step = k == n_acc - 1                   # (always, without accumulation)
-        if n_acc > 1 and k == 0:                   # a new window: both arenas start from zero, every micro-step adds
-            self.discriminator_optimizer.zero_arena()
-            self.generator_optimizer.zero_arena()
+        # (a new window: both arenas start from zero, every micro-step adds)
+        do_step = self.window.begin_call((self.discriminator_optimizer, self.generator_optimizer))
         if self.use_graph and self._graph_ok():
             res = self._graph_step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step)
         else:
             res = self._step(mel_spectrogram, real_audio, speaker_embedding, emotion_embedding, do_step)
-        self._micro = (k + 1) % n_acc
+        self.window.end_call()
         if do_step:
             for sch in self.schedulers:
                 sch.step()
@@ -284,7 +226,9 @@ class VocoderTrainer:
         # (inside an accumulation window the weights are constant: the discriminators' update waits until the generator's gradients
         #  of the window's last micro-step exist too)
         defer = self.accumulation_steps > 1
-        d_scale = self._backward_and_step(d_losses["total_loss"], self.discriminator_optimizer, do_step, defer)
+        d_scale = self.window.backward(d_losses["total_loss"], self.discriminator_optimizer, do_step)   # complete_vocoder.py:217-218
+        if d_scale is not None and not defer:
+            self._apply_step(self.discriminator_optimizer, d_scale)
         # generator step: discriminators re-evaluated after their update; their own weight gradients are not needed
         # (the reference accumulates and then zeroes them at the next D step)
         self.generator_optimizer.zero_grad()
@@ -296,9 +240,10 @@ class VocoderTrainer:
                 g_losses = self.vocoder.compute_generator_losses(real_audio, fake_audio, target, None)
             else:   # the reference's placeholder: generated_mel = mel_spectrogram -> the term is zero
                 g_losses = self.vocoder.compute_generator_losses(real_audio, fake_audio, mel_spectrogram, mel_spectrogram)
-            g_scale = self._backward_and_step(g_losses["total_loss"], self.generator_optimizer, do_step, defer)
-            if defer and do_step:
-                self._apply_step(self.discriminator_optimizer, d_scale)
+            g_scale = self.window.backward(g_losses["total_loss"], self.generator_optimizer, do_step)       # :225-226
+            if g_scale is not None:
+                if defer:
+                    self._apply_step(self.discriminator_optimizer, d_scale)
                 self._apply_step(self.generator_optimizer, g_scale)
         finally:
             for p in self._d_params:
@@ -325,58 +270,73 @@ class VocoderTrainer:
             st = self._graphs[key] = {"warm": 0, "graph": None}
         # warm-up steps and the capture share ONE side stream: autograd pins every parameter's AccumulateGrad node to the stream it
         # was first used on, and a node pinned to the default stream would pull the capture back onto it (and invalidate it)
-        if getattr(self, "_gstream", None) is None:
+        if self._gstream is None:
             self._gstream = torch.cuda.Stream()
-        gs = self._gstream
         if st["graph"] is None and st["warm"] < self.graph_warmup:
-            st["warm"] += 1                       # eager: packs weights, sets launch attributes, sizes every cache
-            gs.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(gs):
-                out = self._step(mel, real, spk, emo, do_step)
-            torch.cuda.current_stream().wait_stream(gs)
-            return out
+            return self._graph_warm(st, (mel, real, spk, emo), do_step)
         gopt, dopt = self.generator_optimizer, self.discriminator_optimizer
-        rng = self.dropout_rng
         if st["graph"] is not None and do_step and not (gopt.runs_match(st["gstate"]) and dopt.runs_match(st["dstate"])):
             # a restored optimizer state split or merged the runs of equal step count that this graph updates: recapture
             torch.cuda.synchronize()              # (its last replay may still be running on the pool it frees)
             st["graph"] = st["out"] = st["gstate"] = st["dstate"] = None
         if st["graph"] is None:
-            st["inputs"] = [None if t is None else t.to(self.device).clone() for t in (mel, real, spk, emo)]
-            self.last_losses = None               # (loss tensors keep last step's autograd graph alive)
-            # every cached cast / packed weight must MISS inside the capture: a hit bakes the pointer of a buffer that the replays never
-            # rewrite (the 16-bit discriminator heads: packed after the warm-up step's update, read again - stale - by every replay's
-            # discriminator step; D loss 1.2 % off from the second replay on), a miss records the pack kernel itself
-            from . import ops as _ops
-            _ops.bump_param_epoch()
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            if os.environ.get("MV_GRAPH_DOT"):
-                graph.enable_debug_mode()
-            gopt.capture_begin(stepping=do_step)
-            dopt.capture_begin(stepping=do_step)
-            if rng is not None:
-                rng.device_block(self.device)     # allocated before the capture: the graph keeps its address
-            try:
-                with torch.cuda.graph(graph, stream=gs):
-                    st["out"] = self._step(*st["inputs"], do_step)
-                st["gstate"], st["dstate"] = gopt.capture_end(), dopt.capture_end()
-                st["dropout_slots"] = rng.slots_used if rng is not None else 0
-            except Exception:
-                gopt._capture = dopt._capture = None
-                self.use_graph = False            # this configuration cannot be captured: stay eager (and say so once)
-                raise
-            st["graph"] = graph
-            if os.environ.get("MV_GRAPH_DOT"):
-                graph.debug_dump(os.environ["MV_GRAPH_DOT"])
-        for dst, src in zip(st["inputs"], (mel, real, spk, emo)):
+            self._graph_capture(st, (mel, real, spk, emo), do_step)
+        return self._graph_replay(st, (mel, real, spk, emo), do_step)
+
+    def _graph_warm(self, st, inputs, do_step):
+        """One eager step on the side stream: packs weights, sets launch attributes, sizes every cache."""
+        st["warm"] += 1
+        gs = self._gstream
+        gs.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(gs):
+            out = self._step(*inputs, do_step)
+        torch.cuda.current_stream().wait_stream(gs)
+        return out
+
+    def _graph_capture(self, st, inputs, do_step):
+        """Record one step on static copies of `inputs` into st["graph"]; st["gstate"] / st["dstate"]: what the optimizers need to
+        replay it.  A configuration that cannot be captured turns use_graph off and raises."""
+        gopt, dopt, rng = self.generator_optimizer, self.discriminator_optimizer, self.dropout_rng
+        st["inputs"] = [None if t is None else t.to(self.device).clone() for t in inputs]
+        self.last_losses = None               # (loss tensors keep last step's autograd graph alive)
+        # every cached cast / packed weight must MISS inside the capture: a hit bakes the pointer of a buffer that the replays never
+        # rewrite (the 16-bit discriminator heads: packed after the warm-up step's update, read again - stale - by every replay's
+        # discriminator step; D loss 1.2 % off from the second replay on), a miss records the pack kernel itself
+        from . import ops as _ops
+        _ops.bump_param_epoch()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        if os.environ.get("MV_GRAPH_DOT"):
+            graph.enable_debug_mode()
+        gopt.capture_begin(stepping=do_step)
+        dopt.capture_begin(stepping=do_step)
+        if rng is not None:
+            rng.device_block(self.device)     # allocated before the capture: the graph keeps its address
+        try:
+            with torch.cuda.graph(graph, stream=self._gstream):
+                st["out"] = self._step(*st["inputs"], do_step)
+            st["gstate"], st["dstate"] = gopt.capture_end(), dopt.capture_end()
+            st["dropout_slots"] = rng.slots_used if rng is not None else 0
+        except Exception:
+            gopt._capture = dopt._capture = None
+            self.use_graph = False            # this configuration cannot be captured: stay eager (and say so once)
+            raise
+        st["graph"] = graph
+        if os.environ.get("MV_GRAPH_DOT"):
+            graph.debug_dump(os.environ["MV_GRAPH_DOT"])
+
+    def _graph_replay(self, st, inputs, do_step):
+        gopt, dopt, rng, gs = self.generator_optimizer, self.discriminator_optimizer, self.dropout_rng, self._gstream
+        for dst, src in zip(st["inputs"], inputs):
             if dst is not None:
                 dst.copy_(src)
         # replayed on the trainer's own stream, fenced against the caller's: on this ROCm build a ~1000-node graph replayed on a stream
         # that also carries other eager training work between replays went wrong from its second replay on (MSD gradients, then NaN) -
         # with the other work on a different stream, or nothing in between, it does not (tests/test_gpu_train_graph.py interleaves
         # an eager trainer with a captured one)
-        def replay():
+        cur = torch.cuda.current_stream()
+        gs.wait_stream(cur)
+        with torch.cuda.stream(gs):
             # the host's per-step state (step counts + 1, lr and the other AdamW inputs, the dropout stream's counter) -> the state
             # blocks the graph reads, on the replay's stream: a few hundred bytes, asynchronously
             if do_step:
@@ -385,10 +345,6 @@ class VocoderTrainer:
             if rng is not None:
                 rng.upload()
             st["graph"].replay()
-        cur = torch.cuda.current_stream()
-        gs.wait_stream(cur)
-        with torch.cuda.stream(gs):
-            replay()
         cur.wait_stream(gs)
         if do_step:
             dopt.after_replay(st["dstate"])
@@ -403,10 +359,7 @@ class VocoderTrainer:
         return {k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in losses.items()}
 
     def save_checkpoint(self, path: str):
-        if self._micro != 0:
-            raise RuntimeError(f"VocoderTrainer.save_checkpoint: in the middle of an accumulation window ({self._micro} of "
-                               f"{self.accumulation_steps} micro-steps taken): the partial gradient sums are not part of a checkpoint - "
-                               "save after the call that steps")
+        self.window.assert_boundary("VocoderTrainer.save_checkpoint")
         ck = {"vocoder_state_dict": self.vocoder.state_dict(),
               # torch.optim.AdamW's layout, so the reference's own load path (complete_vocoder.py:463-468) reads the file too
               "generator_optimizer_state_dict": self.generator_optimizer.torch_state_dict(),
@@ -416,9 +369,7 @@ class VocoderTrainer:
             ck["dropout_rng_state"] = self.dropout_rng.state_dict()
         if self.schedulers:
             ck["scheduler_state_dicts"] = [s.state_dict() for s in self.schedulers]
-        if self.accumulation_steps > 1 or self.max_grad_norm is not None:
-            # informational (the constructor's arguments decide on load); a default trainer writes the keys it always wrote
-            ck["accumulation_steps"], ck["max_grad_norm"] = self.accumulation_steps, self.max_grad_norm
+        ck.update(self.window.checkpoint_extras())
         torch.save(ck, path)
 
     def load_checkpoint(self, path: str):
@@ -430,4 +381,4 @@ class VocoderTrainer:
             self.dropout_rng.load_state_dict(ck["dropout_rng_state"])
         for sch, sd in zip(self.schedulers, ck.get("scheduler_state_dicts", ())):
             sch.load_state_dict(sd)
-        self._micro = 0                      # a checkpoint is always a window boundary
+        self.window.reset()                  # a checkpoint is always a window boundary

@@ -91,22 +91,16 @@ class HiFiGANTrainer:
 
     def __init__(self, model, learning_rate=2e-4, device="cuda", sample_rate=22050, n_fft=1024, grad_sync=None, bucket_mib=8,
                  accumulation_steps=1, max_grad_norm=None):
-        from .optim import FlatAdamW, check_accumulation_args
-        self.accumulation_steps, self.max_grad_norm = check_accumulation_args("HiFiGANTrainer", accumulation_steps, max_grad_norm)
-        self._micro = 0                      # position of the next train_step call inside its accumulation window
+        from .optim import FlatAdamW
+        from .training import GradWindow
+        self.window = w = GradWindow("HiFiGANTrainer", accumulation_steps, max_grad_norm, grad_sync, bucket_mib)
+        self.accumulation_steps, self.max_grad_norm = w.accumulation_steps, w.max_grad_norm
+        self.grad_sync, self._overlap = w.grad_sync, w.overlap     # (data parallel by default when torch.distributed is up)
         self.model = model
         self.device = device
         g = model.generator.generator
         self.optimizer = FlatAdamW(model.parameters(), lr=learning_rate, exclude=list(g.unused_parameters()))
-        self.optimizer.max_grad_norm = self.max_grad_norm
-        if grad_sync is None:       # data parallel by default when torch.distributed is up: buckets reduce under the backward
-            import torch.distributed as dist
-            grad_sync = "overlap" if (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1) else False
-        self.grad_sync = grad_sync
-        self._overlap = None
-        if grad_sync == "overlap" or grad_sync is True:
-            from .parallel import OverlappedGradSync
-            self._overlap = OverlappedGradSync(self.optimizer, bucket_mib=bucket_mib)
+        w.adopt(self.optimizer)
         hop = 1
         for f in g.upsample_factors:
             hop *= f
@@ -140,44 +134,24 @@ class HiFiGANTrainer:
         """MSE(log-mel(fake), mel_input) through the differentiable STFT kernel (conditioned_hifigan.py:237-238)."""
         return Fn.mel_mse(fake_audio, mel_input, self.mel_fb, self.n_fft, self.hop)
 
+    @property
+    def _micro(self):
+        return self.window.position
+
     def train_step(self, mel_input, real_audio, speaker_emb=None, emotion_emb=None):
-        n_acc, k = self.accumulation_steps, self._micro
-        acc, do_step = n_acc > 1, k == n_acc - 1
-        if acc and k == 0:
-            self.optimizer.zero_arena()      # a new window: the arena starts from zero, every micro-step adds
+        do_step = self.window.begin_call((self.optimizer,))     # a new window: the arena starts from zero, every micro-step adds
         self.optimizer.zero_grad()
         fake_audio = self.model(mel_input, speaker_emb=speaker_emb, emotion_emb=emotion_emb)
         total, breakdown = self.compute_losses(real_audio, fake_audio, mel_input)
-        if self._overlap is not None:
-            if acc:
-                self._overlap.begin(accumulate=True, reduce=do_step)
-            else:
-                self._overlap.begin()
-            total.backward()
-            scale = self._overlap.finish()
-        else:
-            total.backward()
-            flat = self.optimizer.gather_grads(accumulate=True) if acc else self.optimizer.gather_grads()
-            scale = 1.0
-            if self.grad_sync and do_step:
-                self.grad_sync.start(flat)
-                scale = self.grad_sync.finish()
-        self._micro = (k + 1) % n_acc
-        if do_step:
-            if acc:
-                scale = scale * (1.0 / n_acc)
-            if self.max_grad_norm is None:
-                self.optimizer.step(grad_scale=scale, gathered=True)
-            else:
-                self.optimizer.step(grad_scale=scale, gathered=True, max_grad_norm=self.optimizer.max_grad_norm)
+        scale = self.window.backward(total, self.optimizer, do_step)
+        self.window.end_call()
+        if scale is not None:
+            self.window.apply(self.optimizer, scale)
         return total.item(), breakdown
 
     def save_checkpoint(self, path, epoch, loss):
-        if self._micro != 0:
-            raise RuntimeError(f"HiFiGANTrainer.save_checkpoint: in the middle of an accumulation window ({self._micro} of "
-                               f"{self.accumulation_steps} micro-steps taken): save after the call that steps")
+        self.window.assert_boundary("HiFiGANTrainer.save_checkpoint")
         ck = {"epoch": epoch, "model_state_dict": self.model.state_dict(),
               "optimizer_state_dict": self.optimizer.torch_state_dict(), "loss": loss}   # torch.optim.AdamW's layout
-        if self.accumulation_steps > 1 or self.max_grad_norm is not None:      # informational; a default trainer's keys are unchanged
-            ck["accumulation_steps"], ck["max_grad_norm"] = self.accumulation_steps, self.max_grad_norm
+        ck.update(self.window.checkpoint_extras())      # informational; a default trainer's keys are unchanged
         torch.save(ck, path)

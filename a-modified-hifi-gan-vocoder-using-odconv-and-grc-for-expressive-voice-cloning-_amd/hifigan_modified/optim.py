@@ -1,10 +1,11 @@
 """Flat-arena AdamW (torch.optim.AdamW semantics: conditioned_hifigan.py:219, train_config.yaml:65-68).
 
 All trainable parameters of a group live in ONE fp32 buffer (each nn.Parameter becomes a view of it), so an
-optimizer step is a single HIP launch (mv_adamw_flat) and the data-parallel exchange is an all-reduce of ONE flat
-gradient buffer, cut into buckets.  Gradients produced by backward are gathered into the flat buffer by one
-multi-tensor launch (mv_multi_gather).  Parameters that never receive a gradient (the unused ODConv attention heads,
-SURVEY.md §5) are left out of the arena exactly like torch.optim skips ``grad is None``.
+optimizer step is a single HIP launch (mv_adamw_flat and its _hp / _clip forms: one kernel, csrc/train.hip) and the
+data-parallel exchange is an all-reduce of ONE flat gradient buffer, cut into buckets.  Gradients produced by backward are
+gathered into the flat buffer by one multi-tensor launch (mv_multi_gather; mv_multi_gather_acc inside an accumulation window).
+Parameters that never receive a gradient (the unused ODConv attention heads) are left out of the arena exactly
+like torch.optim skips ``grad is None``.
 """
 from __future__ import annotations
 
@@ -49,17 +50,6 @@ class DeviceStateBlock:
         slot[1] = ev
 
 
-def check_accumulation_args(who, accumulation_steps, max_grad_norm):
-    """The trainers' two keywords (configs/train_config.yaml: gradient_accumulation_steps; configs/incremental_train_config.yaml:
-    max_grad_norm): a whole number of micro-steps >= 1 and a positive norm (or None: no clipping)."""
-    if isinstance(accumulation_steps, bool) or not isinstance(accumulation_steps, (int, np.integer)) or accumulation_steps < 1:
-        raise ValueError(f"{who}: accumulation_steps must be an integer >= 1, got {accumulation_steps!r}")
-    if max_grad_norm is not None and (isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float, np.floating))
-                                      or not max_grad_norm > 0):
-        raise ValueError(f"{who}: max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
-    return int(accumulation_steps), (None if max_grad_norm is None else float(max_grad_norm))
-
-
 class FlatAdamW:
     def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, exclude=()):
         excl = {id(p) for p in exclude}
@@ -101,8 +91,9 @@ class FlatAdamW:
         self._descs = np.zeros(len(self.params), dtype=_DESC)
         self._descs["dst_off"] = self.offsets
         self._descs["n"] = [p.numel() for p in self.params]
-        self._max_len = int(self._descs["n"].max())
         self._has_grad = None        # per parameter, set by the gathers of the current step (None = every parameter)
+        self._pin_ring = {"slots": [], "next": 0}    # pinned staging buffers of the eager descriptor uploads (_upload)
+        self._tables = []            # the last descriptor tables on the device, kept alive until their launches have consumed them
         # max_grad_norm clipping (step(max_grad_norm=...)): the value a captured step's replays read (before_replay uploads it) and the
         # trainers pass; None = no clipping.  grad_norm: the last step's gradient norm, a 0-d device tensor (never read by the host here)
         self.max_grad_norm = None
@@ -120,34 +111,40 @@ class FlatAdamW:
         OPS.zero_(self.flat_g)
         self._has_grad = [False] * len(self.params)
 
-    def _gather(self, table, n, max_len, accumulate):
+    def _fill_descs(self, d, i0, accumulate, unknown):
+        """Source pointer and dtype of descriptor rows `d` (parameters i0 .. i0 + len(d) - 1) from their .grad - a missing one is a
+        NULL source - and the has-gradient bookkeeping: a parameter has a gradient when this gather gave it one or, accumulating,
+        when an earlier one since the last overwrite / zero_arena() did.  `unknown`: what the parameters count as while no gather of
+        this step has said (self._has_grad is None)."""
+        if self._has_grad is None:
+            self._has_grad = [unknown] * len(self.params)
+        for j, p in enumerate(self.params[i0:i0 + len(d)]):
+            g = p.grad
+            self._has_grad[i0 + j] = (g is not None) or (accumulate and self._has_grad[i0 + j])
+            if g is None:
+                d["src"][j], d["dtype"][j] = 0, 0
+            else:
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                    p.grad = g
+                d["src"][j], d["dtype"][j] = g.data_ptr(), ops._DT[g.dtype]
+
+    def _gather(self, d, accumulate):
+        table = self._upload(d)
+        n, max_len = len(d), int(d["n"].max())
         if accumulate:
             from .torch_ops import OPS
             OPS.multi_gather_acc_(table, n, max_len, self.flat_g)       # mv_multi_gather_acc
         else:
             N.call("mv_multi_gather", c_void_p(table.data_ptr()), n, max_len, c_void_p(self.flat_g.data_ptr()), ops._stream())
+        self._tables = self._tables[-64:] + [table]   # keep alive until the launches have consumed them
 
     def gather_grads(self, accumulate=False):
         """param.grad tensors (fresh per backward) -> flat fp32 buffer; missing grads contribute zeros.  accumulate=True adds to the
         buffer instead (micro-steps of an accumulation window): a missing grad then adds nothing, and a parameter counts as having a
         gradient when any gather since the last overwrite / zero_arena() gave it one."""
-        d = self._descs
-        has = [p.grad is not None for p in self.params]
-        if accumulate and self._has_grad is not None:
-            has = [a or b for a, b in zip(self._has_grad, has)]
-        self._has_grad = has
-        for i, p in enumerate(self.params):
-            g = p.grad
-            if g is None:
-                d["src"][i], d["dtype"][i] = 0, 0
-            else:
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                    p.grad = g
-                d["src"][i], d["dtype"][i] = g.data_ptr(), ops._DT[g.dtype]
-        table = self._upload(d)
-        self._gather(table, len(self.params), self._max_len, accumulate)
-        self._table = table   # keep alive until the launch has consumed it
+        self._fill_descs(self._descs, 0, accumulate, unknown=False)     # every parameter is asked: nothing is taken on trust
+        self._gather(self._descs, accumulate)
         return self.flat_g
 
     def _upload(self, descs):
@@ -166,10 +163,7 @@ class FlatAdamW:
         # eager path: a ring of pinned staging buffers, so that the copy is a real asynchronous H2D (from pageable memory it is staged
         # synchronously - a host stall per bucket while the backward is producing the next gradients).  A slot is reused only after the
         # copy that last read it has completed (event per slot; in steady state it has, long ago).
-        ring = getattr(self, "_pin_ring", None)
-        if ring is None:
-            ring = self._pin_ring = {"slots": [], "next": 0}
-        n = raw.numel()
+        ring, n = self._pin_ring, raw.numel()
         if len(ring["slots"]) < 16:
             ring["slots"].append([torch.empty(max(n, 4096), dtype=torch.uint8).pin_memory(), None])
             slot = ring["slots"][-1]
@@ -192,21 +186,22 @@ class FlatAdamW:
         parallel.OverlappedGradSync while the backward is still running.  Missing gradients contribute zeros; accumulate=True adds
         to the buffer like gather_grads(accumulate=True)."""
         d = self._descs[i0:i1].copy()
-        if self._has_grad is None or len(self._has_grad) != len(self.params):
-            self._has_grad = [True] * len(self.params)
-        for j, p in enumerate(self.params[i0:i1]):
-            g = p.grad
-            self._has_grad[i0 + j] = (g is not None) or (accumulate and self._has_grad[i0 + j])
-            if g is None:
-                d["src"][j], d["dtype"][j] = 0, 0
-            else:
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                    p.grad = g
-                d["src"][j], d["dtype"][j] = g.data_ptr(), ops._DT[g.dtype]
-        table = self._upload(d)
-        self._gather(table, i1 - i0, int(d["n"].max()), accumulate)
-        self._tables = getattr(self, "_tables", [])[-64:] + [table]   # keep alive until the launches have consumed them
+        self._fill_descs(d, i0, accumulate, unknown=True)       # the other buckets' parameters count as having one until asked
+        self._gather(d, accumulate)
+
+    def _runs(self, has=None):
+        """Maximal runs (i0, i1) of consecutive parameters that share a step count, over the parameters with has[i] (None: all)."""
+        runs, i, n = [], 0, len(self.params)
+        while i < n:
+            if has is not None and not has[i]:
+                i += 1
+                continue
+            j = i + 1
+            while j < n and (has is None or has[j]) and self.steps[j] == self.steps[i]:
+                j += 1
+            runs.append((i, j))
+            i = j
+        return runs
 
     def _clip_slots(self):
         """fp32 device buffer: [0] the gradient norm, [1] the clip coefficient, then the norm kernel's workspace."""
@@ -227,18 +222,7 @@ class FlatAdamW:
             self.gather_grads()
         # torch.optim.AdamW leaves a parameter whose .grad is None untouched (no weight decay, no moment decay, no step): update only
         # the runs of parameters that received a gradient this step and share a step count - one launch when all did, the usual case
-        hg = self._has_grad if self._has_grad is not None else [True] * len(self.params)
-        runs, i, n = [], 0, len(self.params)
-        while i < n:
-            if hg[i]:
-                j = i
-                while j + 1 < n and hg[j + 1] and self.steps[j + 1] == self.steps[i]:
-                    j += 1
-                end = self.numel if j == n - 1 else self.offsets[j + 1]
-                runs.append((i, j + 1, self.offsets[i], end - self.offsets[i]))
-                i = j + 1
-            else:
-                i += 1
+        runs = self._runs(self._has_grad)
         from .torch_ops import OPS
         cap = self._capture
         clip = None
@@ -251,8 +235,10 @@ class FlatAdamW:
                     raise RuntimeError("FlatAdamW: set optimizer.max_grad_norm before capture_begin() of a step that clips")
                 cap["clip"] = True
                 OPS.grad_norm(self.flat_g, clip, cap["block"].dev.view(torch.float32)[5:6], 0.0, float(grad_scale))
-        for (i0, i1, off, cnt) in runs:   # torch.ops.mi355x_vocoder.fused_adamw_ (in place on the arena slices; mv_adamw_flat)
+        for (i0, i1) in runs:   # torch.ops.mi355x_vocoder.fused_adamw_ (in place on the arena slices; mv_adamw_flat)
             t = self.steps[i0] + 1
+            off = self.offsets[i0]
+            cnt = (self.numel if i1 == len(self.params) else self.offsets[i1]) - off
             args = (self.flat_p[off:off + cnt], self.flat_g[off:off + cnt], self.exp_avg[off:off + cnt], self.exp_avg_sq[off:off + cnt],
                     float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay))
             if cap is None:
@@ -300,14 +286,7 @@ class FlatAdamW:
 
     def _planned_runs(self):
         """Runs of equal step count over ALL parameters (a captured step must give every parameter of the arena a gradient)."""
-        runs, i, n = [], 0, len(self.params)
-        while i < n:
-            j = i
-            while j + 1 < n and self.steps[j + 1] == self.steps[i]:
-                j += 1
-            runs.append((i, j + 1))
-            i = j + 1
-        return runs
+        return self._runs()
 
     def capture_end(self):
         cap, self._capture = self._capture, None

@@ -18,13 +18,15 @@ Operators (schemas as registered; ``act``: 0 none, 1 LeakyReLU, 2 tanh, 3 SiLU; 
   grc_mrf_block, generator_forward                   fused inference: grc_lora.py:157-163, SURVEY.md appendix A
   avg_pool1d, mpd_fold, disc_conv_stack              discriminators.py:72-79,94,56-66,97-107
   gan_loss, mel_loss, mel_spectrogram                complete_vocoder.py:89-184, conditioned_hifigan.py:262-265; DESIGN.md section 2
-  fused_adamw_, fused_adamw_dev_, fused_adamw_hp_     conditioned_hifigan.py:219 (torch.optim.AdamW semantics)
-  multi_gather_acc_, zero_, grad_norm, fused_adamw_clip_   gradient_accumulation_steps / max_grad_norm of configs/*train_config.yaml
+  fused_adamw_, fused_adamw_dev_, fused_adamw_hp_, fused_adamw_clip_   conditioned_hifigan.py:219 (torch.optim.AdamW semantics): one
+                                                     kernel, the per-step inputs by value or from device memory, clipped or not
+  multi_gather_acc_, zero_, grad_norm                gradient_accumulation_steps / max_grad_norm of configs/*train_config.yaml
 """
 from __future__ import annotations
 
 import threading
 import weakref
+from ctypes import c_void_p
 
 import torch
 
@@ -144,6 +146,35 @@ def _forward_only(name, schema, fn):
     torch.library.register_autograd(f"{NS}::{name}", backward, setup_context=lambda ctx, inputs, output: None, lib=_LIB)
 
 
+def _inplace(name, schema, fn):
+    """In-place operator (`schema` ends in `-> ()`): definition, CUDA implementation, refusing CPU kernel and a fake that returns None."""
+    _LIB.define(name + schema)
+    _LIB.impl(name, fn, "CUDA")
+    _LIB.impl(name, _refuse_cpu(name), "CPU")
+    torch.library.register_fake(f"{NS}::{name}", lambda *args, **kwargs: None, lib=_LIB)
+
+
+def _ptr(t):
+    return c_void_p(t.data_ptr()) if t is not None else None
+
+
+# argument checks of the optimizer operators; None passes (an argument its schema marks optional)
+def _check_arena(name, p, g, m, v):
+    if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
+            any(t.dtype != torch.float32 or t.numel() != p.numel() for t in (p, g, m, v)):
+        raise RuntimeError(f"{NS}::{name}: p, g, exp_avg, exp_avg_sq must be contiguous fp32 tensors of one size")
+
+
+def _check_one(name, arg, t, dtype):
+    if t is not None and (t.dtype != dtype or t.numel() != 1 or not t.is_cuda):
+        raise RuntimeError(f"{NS}::{name}: {arg} must be a one-element {'int32' if dtype == torch.int32 else 'fp32'} GPU tensor")
+
+
+def _check_hparams(name, hp):
+    if hp is not None and (hp.dtype != torch.float32 or hp.numel() != 5 or not hp.is_contiguous() or not hp.is_cuda):
+        raise RuntimeError(f"{NS}::{name}: hparams must be a contiguous five-element fp32 GPU tensor")
+
+
 def _install():
     from . import functional as Fn
     from . import disc_fused
@@ -193,118 +224,74 @@ def _install():
         return _obj(handle).forward(mel, spk, emo, cache=Fn._cache)
     _forward_only("generator_forward", "(Tensor mel, Tensor? speaker_emb, Tensor? emotion_emb, int handle) -> Tensor", generator_forward)
 
-    # ---- optimizer
-    _LIB.define("fused_adamw_(Tensor(a!) p, Tensor g, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, float lr, float beta1, float beta2, "
-                "float eps, float weight_decay, int step, float grad_scale) -> ()")
+    # ---- optimizer (conditioned_hifigan.py:219, torch.optim.AdamW semantics) on optim.FlatAdamW's arena: ONE kernel behind the four
+    # forms, which differ in where lr ... weight_decay, the step count and the clip coefficient come from
+    arena = "Tensor(a!) p, Tensor g, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq"
+    by_value = "float lr, float beta1, float beta2, float eps, float weight_decay"
 
     def fused_adamw_(p, g, m, v, lr, b1, b2, eps, wd, step, gscale):
-        from ctypes import c_void_p
-        if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
-                any(t.dtype != torch.float32 or t.numel() != p.numel() for t in (p, g, m, v)):
-            raise RuntimeError(f"{NS}::fused_adamw_: p, g, exp_avg, exp_avg_sq must be contiguous fp32 tensors of one size")
-        N.call("mv_adamw_flat", c_void_p(p.data_ptr()), c_void_p(g.data_ptr()), c_void_p(m.data_ptr()), c_void_p(v.data_ptr()),
-               p.numel(), float(lr), float(b1), float(b2), float(eps), float(wd), int(step), float(gscale), ops._stream())
-    _LIB.impl("fused_adamw_", fused_adamw_, "CUDA")
-    _LIB.impl("fused_adamw_", _refuse_cpu("fused_adamw_"), "CPU")
+        _check_arena("fused_adamw_", p, g, m, v)
+        N.call("mv_adamw_flat", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(b1), float(b2), float(eps), float(wd),
+               int(step), float(gscale), ops._stream())
+    _inplace("fused_adamw_", f"({arena}, {by_value}, int step, float grad_scale) -> ()", fused_adamw_)
 
     # the step count as a device tensor (int32, already incremented): what a captured training step replays
-    _LIB.define("fused_adamw_dev_(Tensor(a!) p, Tensor g, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, float lr, float beta1, float beta2, "
-                "float eps, float weight_decay, Tensor step, float grad_scale) -> ()")
-
     def fused_adamw_dev_(p, g, m, v, lr, b1, b2, eps, wd, step, gscale):
-        from ctypes import c_void_p
-        if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
-                any(t.dtype != torch.float32 or t.numel() != p.numel() for t in (p, g, m, v)):
-            raise RuntimeError(f"{NS}::fused_adamw_dev_: p, g, exp_avg, exp_avg_sq must be contiguous fp32 tensors of one size")
-        if step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
-            raise RuntimeError(f"{NS}::fused_adamw_dev_: step must be a one-element int32 GPU tensor")
-        N.call("mv_adamw_flat_dev", c_void_p(p.data_ptr()), c_void_p(g.data_ptr()), c_void_p(m.data_ptr()), c_void_p(v.data_ptr()),
-               p.numel(), float(lr), float(b1), float(b2), float(eps), float(wd), c_void_p(step.data_ptr()), float(gscale), ops._stream())
-    _LIB.impl("fused_adamw_dev_", fused_adamw_dev_, "CUDA")
-    _LIB.impl("fused_adamw_dev_", _refuse_cpu("fused_adamw_dev_"), "CPU")
+        _check_arena("fused_adamw_dev_", p, g, m, v)
+        _check_one("fused_adamw_dev_", "step", step, torch.int32)
+        N.call("mv_adamw_flat_dev", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(b1), float(b2), float(eps),
+               float(wd), _ptr(step), float(gscale), ops._stream())
+    _inplace("fused_adamw_dev_", f"({arena}, {by_value}, Tensor step, float grad_scale) -> ()", fused_adamw_dev_)
 
     # every per-step input in device memory (hparams: fp32 {lr, beta1, beta2, eps, weight_decay}; step: int32, already incremented):
     # what a captured training step replays, the host refreshing both before each replay
-    _LIB.define("fused_adamw_hp_(Tensor(a!) p, Tensor g, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor hparams, Tensor step, "
-                "float grad_scale) -> ()")
-
     def fused_adamw_hp_(p, g, m, v, hparams, step, gscale):
-        from ctypes import c_void_p
-        if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
-                any(t.dtype != torch.float32 or t.numel() != p.numel() for t in (p, g, m, v)):
-            raise RuntimeError(f"{NS}::fused_adamw_hp_: p, g, exp_avg, exp_avg_sq must be contiguous fp32 tensors of one size")
-        if hparams.dtype != torch.float32 or hparams.numel() != 5 or not hparams.is_contiguous() or not hparams.is_cuda:
-            raise RuntimeError(f"{NS}::fused_adamw_hp_: hparams must be a contiguous five-element fp32 GPU tensor")
-        if step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
-            raise RuntimeError(f"{NS}::fused_adamw_hp_: step must be a one-element int32 GPU tensor")
-        N.call("mv_adamw_flat_hp", c_void_p(p.data_ptr()), c_void_p(g.data_ptr()), c_void_p(m.data_ptr()), c_void_p(v.data_ptr()),
-               p.numel(), c_void_p(hparams.data_ptr()), c_void_p(step.data_ptr()), float(gscale), ops._stream())
-    _LIB.impl("fused_adamw_hp_", fused_adamw_hp_, "CUDA")
-    _LIB.impl("fused_adamw_hp_", _refuse_cpu("fused_adamw_hp_"), "CPU")
+        _check_arena("fused_adamw_hp_", p, g, m, v)
+        _check_hparams("fused_adamw_hp_", hparams)
+        _check_one("fused_adamw_hp_", "step", step, torch.int32)
+        N.call("mv_adamw_flat_hp", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(hparams), _ptr(step), float(gscale), ops._stream())
+    _inplace("fused_adamw_hp_", f"({arena}, Tensor hparams, Tensor step, float grad_scale) -> ()", fused_adamw_hp_)
+
+    # AdamW with g scaled by grad_scale * coef[0]; hparams / step_dev as in fused_adamw_hp_, each optional (None: the float / int arguments)
+    def fused_adamw_clip_(p, g, m, v, hparams, step_dev, lr, b1, b2, eps, wd, step, gscale, coef):
+        _check_arena("fused_adamw_clip_", p, g, m, v)
+        _check_hparams("fused_adamw_clip_", hparams)
+        _check_one("fused_adamw_clip_", "step_dev", step_dev, torch.int32)
+        _check_one("fused_adamw_clip_", "coef", coef, torch.float32)
+        N.call("mv_adamw_flat_clip", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(hparams), _ptr(step_dev), float(lr), float(b1),
+               float(b2), float(eps), float(wd), int(step), float(gscale), _ptr(coef), ops._stream())
+    _inplace("fused_adamw_clip_", f"({arena}, Tensor? hparams, Tensor? step_dev, {by_value}, int step, float grad_scale, Tensor coef) -> ()",
+             fused_adamw_clip_)
 
     # ---- gradient accumulation and max_grad_norm clipping on the arena (optim.FlatAdamW)
     # table: the uint8 image of n_tensors gather descriptors {src pointer, dst_off, n, dtype} on the device; flat += the sources
-    _LIB.define("multi_gather_acc_(Tensor table, int n_tensors, int max_len, Tensor(a!) flat) -> ()")
-
     def multi_gather_acc_(table, n_tensors, max_len, flat):
-        from ctypes import c_void_p
         if table.dtype != torch.uint8 or not table.is_contiguous() or table.numel() != 32 * n_tensors or not table.is_cuda:
             raise RuntimeError(f"{NS}::multi_gather_acc_: table must be the contiguous uint8 image of n_tensors 32-byte descriptors on the GPU")
         if flat.dtype != torch.float32 or not flat.is_contiguous():
             raise RuntimeError(f"{NS}::multi_gather_acc_: flat must be a contiguous fp32 tensor")
-        N.call("mv_multi_gather_acc", c_void_p(table.data_ptr()), int(n_tensors), int(max_len), c_void_p(flat.data_ptr()), ops._stream())
-    _LIB.impl("multi_gather_acc_", multi_gather_acc_, "CUDA")
-    _LIB.impl("multi_gather_acc_", _refuse_cpu("multi_gather_acc_"), "CPU")
-
-    _LIB.define("zero_(Tensor(a!) x) -> ()")
+        N.call("mv_multi_gather_acc", _ptr(table), int(n_tensors), int(max_len), _ptr(flat), ops._stream())
+    _inplace("multi_gather_acc_", "(Tensor table, int n_tensors, int max_len, Tensor(a!) flat) -> ()", multi_gather_acc_)
 
     def zero_(x):
-        from ctypes import c_void_p
         if x.dtype != torch.float32 or not x.is_contiguous() or x.data_ptr() % 16:
             raise RuntimeError(f"{NS}::zero_: x must be a contiguous, 16-byte aligned fp32 tensor")
-        N.call("mv_zero_f32", c_void_p(x.data_ptr()), x.numel(), ops._stream())
-    _LIB.impl("zero_", zero_, "CUDA")
-    _LIB.impl("zero_", _refuse_cpu("zero_"), "CPU")
+        N.call("mv_zero_f32", _ptr(x), x.numel(), ops._stream())
+    _inplace("zero_", "(Tensor(a!) x) -> ()", zero_)
 
     # out (fp32, >= 2 + GRAD_NORM_WS_WORDS elements): out[0] = norm of pre_scale * g, out[1] = min(1, max_norm / (norm + 1e-6)), the rest is
     # the kernel's workspace; max_norm_dev (one fp32 element on the GPU) overrides max_norm: what a captured step replays
-    _LIB.define("grad_norm(Tensor g, Tensor(a!) out, Tensor? max_norm_dev, float max_norm, float pre_scale) -> ()")
-
     def grad_norm(g, out, max_norm_dev, max_norm, pre_scale):
-        from ctypes import c_void_p
         if g.dtype != torch.float32 or not g.is_contiguous() or g.data_ptr() % 16 or g.numel() == 0:
             raise RuntimeError(f"{NS}::grad_norm: g must be a non-empty contiguous, 16-byte aligned fp32 tensor")
         if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < 2 + GRAD_NORM_WS_WORDS or out.data_ptr() % 8 or not out.is_cuda:
             raise RuntimeError(f"{NS}::grad_norm: out must be a contiguous fp32 GPU tensor of at least {2 + GRAD_NORM_WS_WORDS} elements")
-        if max_norm_dev is not None and (max_norm_dev.dtype != torch.float32 or max_norm_dev.numel() != 1 or not max_norm_dev.is_cuda):
-            raise RuntimeError(f"{NS}::grad_norm: max_norm_dev must be a one-element fp32 GPU tensor")
+        _check_one("grad_norm", "max_norm_dev", max_norm_dev, torch.float32)
         if max_norm_dev is None and not max_norm > 0:
             raise RuntimeError(f"{NS}::grad_norm: max_norm must be positive, got {max_norm}")
-        N.call("mv_grad_norm", c_void_p(g.data_ptr()), g.numel(), float(pre_scale), c_void_p(max_norm_dev.data_ptr()) if max_norm_dev is not None else None,
-               float(max_norm), c_void_p(out.data_ptr() + 8), c_void_p(out.data_ptr()), ops._stream())
-    _LIB.impl("grad_norm", grad_norm, "CUDA")
-    _LIB.impl("grad_norm", _refuse_cpu("grad_norm"), "CPU")
-
-    # AdamW with g scaled by grad_scale * coef[0]; hparams / step_dev as in fused_adamw_hp_, each optional (None: the float / int arguments)
-    _LIB.define("fused_adamw_clip_(Tensor(a!) p, Tensor g, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor? hparams, Tensor? step_dev, "
-                "float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, Tensor coef) -> ()")
-
-    def fused_adamw_clip_(p, g, m, v, hparams, step_dev, lr, b1, b2, eps, wd, step, gscale, coef):
-        from ctypes import c_void_p
-        if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
-                any(t.dtype != torch.float32 or t.numel() != p.numel() for t in (p, g, m, v)):
-            raise RuntimeError(f"{NS}::fused_adamw_clip_: p, g, exp_avg, exp_avg_sq must be contiguous fp32 tensors of one size")
-        if hparams is not None and (hparams.dtype != torch.float32 or hparams.numel() != 5 or not hparams.is_contiguous() or not hparams.is_cuda):
-            raise RuntimeError(f"{NS}::fused_adamw_clip_: hparams must be a contiguous five-element fp32 GPU tensor")
-        if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.numel() != 1 or not step_dev.is_cuda):
-            raise RuntimeError(f"{NS}::fused_adamw_clip_: step_dev must be a one-element int32 GPU tensor")
-        if coef.dtype != torch.float32 or coef.numel() != 1 or not coef.is_cuda:
-            raise RuntimeError(f"{NS}::fused_adamw_clip_: coef must be a one-element fp32 GPU tensor")
-        N.call("mv_adamw_flat_clip", c_void_p(p.data_ptr()), c_void_p(g.data_ptr()), c_void_p(m.data_ptr()), c_void_p(v.data_ptr()), p.numel(),
-               c_void_p(hparams.data_ptr()) if hparams is not None else None, c_void_p(step_dev.data_ptr()) if step_dev is not None else None,
-               float(lr), float(b1), float(b2), float(eps), float(wd), int(step), float(gscale), c_void_p(coef.data_ptr()), ops._stream())
-    _LIB.impl("fused_adamw_clip_", fused_adamw_clip_, "CUDA")
-    _LIB.impl("fused_adamw_clip_", _refuse_cpu("fused_adamw_clip_"), "CPU")
+        N.call("mv_grad_norm", _ptr(g), g.numel(), float(pre_scale), _ptr(max_norm_dev), float(max_norm), c_void_p(out.data_ptr() + 8),
+               _ptr(out), ops._stream())
+    _inplace("grad_norm", "(Tensor g, Tensor(a!) out, Tensor? max_norm_dev, float max_norm, float pre_scale) -> ()", grad_norm)
 
 
 def _install_fakes():
@@ -378,34 +365,6 @@ def _install_fakes():
         for f in _obj(handle).gen.upsample_factors:
             total *= f
         return mel.new_empty(mel.shape[0], 1, mel.shape[2] * total)
-
-    @fake("fused_adamw_")
-    def _(p, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale):
-        return None
-
-    @fake("fused_adamw_dev_")
-    def _(p, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale):
-        return None
-
-    @fake("fused_adamw_hp_")
-    def _(p, g, exp_avg, exp_avg_sq, hparams, step, grad_scale):
-        return None
-
-    @fake("multi_gather_acc_")
-    def _(table, n_tensors, max_len, flat):
-        return None
-
-    @fake("zero_")
-    def _(x):
-        return None
-
-    @fake("grad_norm")
-    def _(g, out, max_norm_dev, max_norm, pre_scale):
-        return None
-
-    @fake("fused_adamw_clip_")
-    def _(p, g, exp_avg, exp_avg_sq, hparams, step_dev, lr, beta1, beta2, eps, weight_decay, step, grad_scale, coef):
-        return None
 
 
 _install()

@@ -154,17 +154,36 @@ __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
     default: return MV_ERR_DTYPE;                                       \
   }
 
-// internal cross-file entry (conv_out.hip), not part of the C ABI
-// (part8 / tab8 / nwg / eps: the fp32 MFMA form forms the deferred GroupNorm affine itself from the last block's partial sums and
-//  `ab` is not read - mvi_conv_out_affine_takes_partials says whether that form will run)
+// ---- the MRF chain's host side (mrf_fused.hip, mrf_stream.hip, conv_out.hip); none of it is part of the C ABI
+// How the rows of x, the last block's residual input, reach the chain's consumer; f is fp32 rows in every form (hl8 rows for f
+// measured slower, DESIGN.md section 4, lesson 33).  The values are the XFMT argument of conv_out_affine_mfma_kernel.
+enum MrfRowForm {
+  MRF_ROWS_FP32 = 0,   // x and f fp32 rows
+  MRF_ROWS_PAIR = 1,   // x pair rows: per 8-channel group [8 x f16 hi | 8 x f16 lo], 256 bytes per time step
+  MRF_ROWS_HL8 = 4     // x hl8 rows (mfma.h: f16 hi plane + e4m3 lo plane, 192 bytes per time step)
+};
+// The end of a chain that did not materialise its output: out = a f + b + x is left to the consumer, (a, b) being the last block's
+// deferred GroupNorm(8,64) affine.  part8 / tab / nwg: that block's per-workgroup partial sums and its tables, for a consumer that
+// forms (a, b) itself; null / 0 when the chain has written (a, b) to the workspace's `ab` instead.
+struct MrfChainTail { const void* f; const void* x; MrfRowForm form; const float* part8; const float* tab; int nwg; };
+// Byte offsets into the chain's workspace: f, the two x' buffers, the partial sums (part5, then part8 behind B * nwg * 32 floats
+// with the running form's own nwg), the [B][2][64] affine.  total = mv_mrf_chain_workspace_bytes.
+struct MrfChainWs { size_t f, x[2], part5, ab, total; };
+inline MrfChainWs mrf_chain_ws(int B, int T_, int dtype) {
+  const size_t es = (dtype == MV_F32 || dtype == MV_F32_W16) ? 4 : 2;
+  const size_t act = ((size_t)B * T_ * 64 * es + 255) / 256 * 256;
+  const size_t ab = 3 * act + (mv_mrf_workspace_bytes(B, T_, dtype) + 255) / 256 * 256;
+  return MrfChainWs{0, {act, 2 * act}, 3 * act, ab, ab + (size_t)B * 128 * sizeof(float)};
+}
+// conv_out.hip: the chain's fused ending, y = act(conv(a f + b + x)).  `ab` is read unless tail.part8 is set, which only the form
+// that mvi_conv_out_affine_takes_partials announces accepts; that form alone reads row forms other than MRF_ROWS_FP32.
 bool mvi_conv_out_affine_takes_partials(int dtype, int ks);
-int mvi_conv_out_affine(const void* f, const void* x, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
-                        int pad, int act, int dtype, hipStream_t stream, const float* part8 = nullptr, const float* tab8 = nullptr,
-                        int nwg = 0, float eps = 0.f, int x_pair = 0);
-// internal cross-file entry (mrf_stream.hip): the MRF chain in its streaming form (MV_F32_W16, dilations (1, 3, 5) only)
-int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, int nblocks, char* ws, size_t act_bytes, int B, int Tn,
-                         float eps, hipStream_t stream, const void** f_last, const void** x_last, int* x_last_pair,
-                         const float** part8_last, const float** tab_last, int* nwg_last, int x_pair_in = 0);
+int mvi_conv_out_affine(const MrfChainTail& tail, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
+                        int pad, int act, int dtype, float eps, hipStream_t stream);
+// mrf_stream.hip: the chain in its streaming form (MV_F32_W16, dilations (1, 3, 5) only).  out non-null: the last block's output is
+// written as fp32 rows; otherwise *tail is filled.  x_pair_in: x arrives as pair rows.
+int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, int nblocks, char* ws, const MrfChainWs& lay, int B, int Tn,
+                         float eps, hipStream_t stream, bool x_pair_in, MrfChainTail* tail);
 
 // Zero fill as a KERNEL launch.  hipMemsetAsync becomes a memset node when a stream is being captured, and on this ROCm build a memset
 // node is not reliably ordered in front of the kernel node that follows it in a replayed graph: a captured training step whose

@@ -248,8 +248,8 @@ __global__ void conv_out_pack_all_kernel(const P* __restrict__ w, char* __restri
 //   z[tap][pos] = sum_c w[tap][c] * row[pos][c]   (A = the weights as a 16 x 64 operand, zero beyond ks; B = the staged rows, PRE-SPLIT
 //   into hi + lo bf16 planes when they are committed; 2 k-steps x 3 products per 16 positions, every row read ONCE),
 //   y[t] = bias + sum_tap z[tap][t + tap]          (the z tile replaces the rows in LDS after a barrier; 11 adds per output).
-// XFMT: 0 = f and x fp32 rows; 1 = x as pair rows (8 groups of [8 x f16 hi | 8 x f16 lo], mrf_stream.hip), f fp32; 2 = f and x as hl8
-// rows (mfma.h: 192 bytes, f16 hi plane + e4m3 lo plane); 3 = f hl8, x fp32 (a one-block chain); 4 = x hl8, f fp32
+// XFMT: the MrfRowForm of x (common.h): 0 = fp32 rows; 1 = pair rows (8 groups of [8 x f16 hi | 8 x f16 lo], mrf_stream.hip); 4 = hl8
+// rows (mfma.h: 192 bytes, f16 hi plane + e4m3 lo plane).  f is fp32 rows in every form.
 template <int C, int XFMT>
 __global__ __launch_bounds__(256) void conv_out_affine_mfma_kernel(const float* __restrict__ f, const float* __restrict__ x,
                                                                    const float* __restrict__ ab, const float* __restrict__ w, float bias,
@@ -314,17 +314,16 @@ __global__ __launch_bounds__(256) void conv_out_affine_mfma_kernel(const float* 
         const f32x2_t l0 = __builtin_amdgcn_cvt_pk_f32_fp8(l, false), l1 = __builtin_amdgcn_cvt_pk_f32_fp8(l, true);
         return f32x4{(float)h[0] + l0[0] * SR_LOI, (float)h[1] + l0[1] * SR_LOI, (float)h[2] + l1[0] * SR_LOI, (float)h[3] + l1[1] * SR_LOI};
       };
-      if constexpr (XFMT == 2 || XFMT == 4) {
+      if constexpr (XFMT == MRF_ROWS_HL8) {
         xv[u] = hl4(x);
-      } else if constexpr (XFMT == 1) {
+      } else if constexpr (XFMT == MRF_ROWS_PAIR) {
         const char* px = reinterpret_cast<const char*>(xb) + (size_t)(ok[u] ? t : 0) * (C * 4) + (ch >> 1) * 32 + (ch & 1) * 8;
         const f16x4_t h = *reinterpret_cast<const f16x4_t*>(px), l = *reinterpret_cast<const f16x4_t*>(px + 16);
         xv[u] = f32x4{(float)h[0] + (float)l[0], (float)h[1] + (float)l[1], (float)h[2] + (float)l[2], (float)h[3] + (float)l[3]};
       } else {
         xv[u] = *reinterpret_cast<const f32x4*>(xb + off);
       }
-      if constexpr (XFMT == 2 || XFMT == 3) fv[u] = hl4(f);
-      else fv[u] = *reinterpret_cast<const f32x4*>(fb + off);
+      fv[u] = *reinterpret_cast<const f32x4*>(fb + off);
     }
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
@@ -380,27 +379,30 @@ bool mvi_conv_out_affine_takes_partials(int dtype, int ks) {
   return dtype == MV_F32 && ks <= 16;
 }
 
-int mvi_conv_out_affine(const void* f, const void* x, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
-                        int pad, int act, int dtype, hipStream_t stream, const float* part8, const float* tab8, int nwg, float eps,
-                        int x_pair) {
+int mvi_conv_out_affine(const MrfChainTail& tail, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
+                        int pad, int act, int dtype, float eps, hipStream_t stream) {
   if (C != 64 || 2 * pad != ks - 1) return MV_ERR_UNSUPPORTED;
-  if (x_pair && !(dtype == MV_F32 && mvi_conv_out_affine_takes_partials(dtype, ks))) return MV_ERR_UNSUPPORTED;
-  if (part8 && !mvi_conv_out_affine_takes_partials(dtype, ks)) return MV_ERR_UNSUPPORTED;
+  const bool partials = mvi_conv_out_affine_takes_partials(dtype, ks);
+  if ((tail.form != MRF_ROWS_FP32 || tail.part8) && !partials) return MV_ERR_UNSUPPORTED;
   dim3 grid(cdiv(T_, 256), B);
-  if (dtype == MV_F32 && ks <= 16) {
+  if (partials) {
     const size_t rows16 = (size_t)((256 + ks - 1 + 15) / 16) * 16;
     const size_t lds = rows16 * (2 * 64 * 2 + 16);       // >= the z tile (16 x 288 floats)
-    if (x_pair < 0 || x_pair > 4) return MV_ERR_ARG;
-    auto kern = x_pair == 4 ? conv_out_affine_mfma_kernel<64, 4> : x_pair == 3 ? conv_out_affine_mfma_kernel<64, 3>
-              : x_pair == 2 ? conv_out_affine_mfma_kernel<64, 2> : x_pair == 1 ? conv_out_affine_mfma_kernel<64, 1>
-              : conv_out_affine_mfma_kernel<64, 0>;
-    static size_t lds_set_m[5] = {0, 0, 0, 0, 0};
-    if (lds > lds_set_m[x_pair]) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      lds_set_m[x_pair] = lds;
+    decltype(&conv_out_affine_mfma_kernel<64, MRF_ROWS_FP32>) kern;
+    int slot;
+    switch (tail.form) {
+      case MRF_ROWS_FP32: kern = conv_out_affine_mfma_kernel<64, MRF_ROWS_FP32>; slot = 0; break;
+      case MRF_ROWS_PAIR: kern = conv_out_affine_mfma_kernel<64, MRF_ROWS_PAIR>; slot = 1; break;
+      case MRF_ROWS_HL8: kern = conv_out_affine_mfma_kernel<64, MRF_ROWS_HL8>; slot = 2; break;
+      default: return MV_ERR_ARG;
     }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const float*)f, (const float*)x, ab, wt, bias, (float*)y, T_, ks, pad, act,
-                       part8, tab8, nwg, eps);
+    static size_t lds_set_m[3] = {0, 0, 0};
+    if (lds > lds_set_m[slot]) {
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      lds_set_m[slot] = lds;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const float*)tail.f, (const float*)tail.x, ab, wt, bias, (float*)y, T_, ks,
+                       pad, act, tail.part8, tail.tab, tail.nwg, eps);
     return MV_OK;
   }
   MV_DISPATCH(dtype, {
@@ -409,7 +411,7 @@ int mvi_conv_out_affine(const void* f, const void* x, const float* ab, const flo
     auto kern = conv_out_affine_kernel<T, 64>;
     static size_t lds_set = 0;
     if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)f, (const T*)x, ab, wt, bias, (T*)y, T_, ks, pad, act);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)tail.f, (const T*)tail.x, ab, wt, bias, (T*)y, T_, ks, pad, act);
   });
   return MV_OK;
 }

@@ -712,7 +712,6 @@ static int mrf_launch(const void* x, void* out, const void* packed, const MrfMet
 }
 
 // ---- the chained form: blocks 0..n-1 in a row, GroupNorm(8,64) of block i deferred into pass A of block i+1 (header comment)
-static inline size_t mrf_act_bytes(int B, int Tn, size_t es) { return (((size_t)B * Tn * MRF_C * es) + 255) / 256 * 256; }
 
 template <typename T, int NWAVES, int NTW, int PASS>
 static void mrf_chain_pass(bool stdm, dim3 grid, size_t lds, hipStream_t stream, const StT<T>* x, StT<T>* out, const char* packed,
@@ -745,12 +744,28 @@ __global__ __launch_bounds__(64) void mrf_affine_kernel(const float* __restrict_
   ab[(size_t)b * 128 + 64 + c] = tab[384 + c] - mu * a;
 }
 
-// `ab_out` non-null: no pass F; the caller gets the last block's (f, x) buffers and its deferred affine instead
+// The validated request of the two chain entries, what the caller wants at the end of the chain, and the chain in its tile form.
+struct MrfChainReq {
+  const void* x; void* out; const void* const* packed; MrfMeta metas[8]; int nblocks; char* ws; int B, T; float eps;
+  int dtype;                 // storage dtype (MV_F32_W16P decoded: MV_F32_W16 with x_pair_in)
+  bool x_pair_in;            // x arrives as pair rows (streaming form only)
+  hipStream_t stream;
+};
+enum MrfChainKind {
+  MATERIALIZE,               // pass F writes the last block's output to `out`
+  PASSES_ONLY,               // the passes run and leave (f, x, partial sums) in the workspace; nothing else is launched
+  TAIL_WITH_AB,              // no pass F: the caller gets the tail, and mrf_affine_kernel writes the deferred affine to the workspace
+  TAIL_WITH_PARTIALS         // no pass F: the caller gets the tail and forms the affine itself from the partial sums
+};
+
 template <typename T, int NWAVES, int NTW>
-static int mrf_chain_launch(const void* x, void* out, const void* const* packed, const MrfMeta* metas, int nblocks, char* ws,
-                            int B, int Tn, float eps, hipStream_t stream, float* ab_out = nullptr, const void** f_last = nullptr,
-                            const void** x_last = nullptr, const float** part8_last = nullptr, const float** tab_last = nullptr,
-                            int* nwg_last = nullptr) {
+static int mrf_chain_launch(const MrfChainReq& r, const MrfChainWs& lay, MrfChainKind kind, MrfChainTail* tail) {
+  const void* const* packed = r.packed;
+  const MrfMeta* metas = r.metas;
+  char* const ws = r.ws;
+  const int nblocks = r.nblocks, B = r.B, Tn = r.T;
+  const float eps = r.eps;
+  const hipStream_t stream = r.stream;
   using M = Mma<T>;
   constexpr int FS = M::NSETS * FRAG_BYTES;
   constexpr int RS = (M::ES == 4 ? 2 * MRF_C * 2 : MRF_C * M::ES) + 32;   // as in the kernel
@@ -762,10 +777,9 @@ static int mrf_chain_launch(const void* x, void* out, const void* const* packed,
                      (size_t)NWAVES * 32 * 4 + tile_rows * RS;
   if (lds > 160 * 1024 || hmax > MRF_HMAX) return MV_ERR_UNSUPPORTED;
   using ST = StT<T>;
-  const size_t act = mrf_act_bytes(B, Tn, sizeof(ST));
-  ST* fbuf = reinterpret_cast<ST*>(ws);
-  ST* xbuf[2] = {reinterpret_cast<ST*>(ws + act), reinterpret_cast<ST*>(ws + 2 * act)};
-  float* part5 = reinterpret_cast<float*>(ws + 3 * act);
+  ST* fbuf = reinterpret_cast<ST*>(ws + lay.f);
+  ST* xbuf[2] = {reinterpret_cast<ST*>(ws + lay.x[0]), reinterpret_cast<ST*>(ws + lay.x[1])};
+  float* part5 = reinterpret_cast<float*>(ws + lay.part5);
   float* part8 = part5 + (size_t)B * nwg * 32;
   const dim3 grid(nwg, B);
   // fp32: the statistics-of-v passes (1, 4) keep only the branch-conv fragments in LDS and run 32-step wave tiles (see the kernel);
@@ -774,7 +788,7 @@ static int mrf_chain_launch(const void* x, void* out, const void* const* packed,
   const size_t lds_wide = (size_t)MRF_CONV_FRAGS * FS + MRF_TAB_FLOATS * 4 + (32 + 16) * 4 + (size_t)NWAVES * 32 * 4 +
                           ((size_t)NWAVES * 2 * 16 + 2 * hmax) * RS;
   const bool wide = WIDE_OK && nit >= 2 && nit % 2 == 0 && lds_wide <= 160 * 1024 && Tn % (NWAVES * 32) == 0;
-  const ST* xi = (const ST*)x;                       // x_i: the input of block i
+  const ST* xi = (const ST*)r.x;                     // x_i: the input of block i
   for (int i = 0; i < nblocks; ++i) {
     const bool stdm = mrf_meta_is_std(metas[i]);
     const char* pk = (const char*)packed[i];
@@ -796,18 +810,20 @@ static int mrf_chain_launch(const void* x, void* out, const void* const* packed,
     mrf_chain_pass<T, NWAVES, NTW, 5>(stdm, grid, lds, stream, xi, fbuf, pk, metas[i], part5, nullptr, nullptr, part8, Tn, nwg, nit, eps,
                                       nullptr, nullptr);
   }
-  if (ab_out) {
+  if (kind != MATERIALIZE) {
     constexpr size_t WB = (size_t)(MRF_CONV_FRAGS + MRF_RES_FRAGS + MRF_FUS_FRAGS) * FS;
     const float* tabp = reinterpret_cast<const float*>((const char*)packed[nblocks - 1] + WB);
-    if (part8_last) { *part8_last = part8; *tab_last = tabp; *nwg_last = nwg; }      // the consumer forms the affine itself
-    else hipLaunchKernelGGL(mrf_affine_kernel, dim3(B), dim3(64), 0, stream, part8, tabp, ab_out, nwg, Tn, eps);
-    *f_last = fbuf;
-    *x_last = xi;
+    if (kind == TAIL_WITH_AB) {
+      hipLaunchKernelGGL(mrf_affine_kernel, dim3(B), dim3(64), 0, stream, part8, tabp, reinterpret_cast<float*>(ws + lay.ab), nwg, Tn, eps);
+      *tail = MrfChainTail{fbuf, xi, MRF_ROWS_FP32, nullptr, nullptr, 0};
+    } else {
+      *tail = MrfChainTail{fbuf, xi, MRF_ROWS_FP32, part8, tabp, nwg};
+    }
     return MV_OK;
   }
   MrfMeta mf = metas[nblocks - 1];
   mf.halo = 0;                                       // pass F touches this wave's own rows only
-  mrf_chain_pass<T, NWAVES, NTW, 6>(true, grid, lds, stream, xi, (ST*)out, (const char*)packed[nblocks - 1], mf, nullptr, nullptr, part8,
+  mrf_chain_pass<T, NWAVES, NTW, 6>(true, grid, lds, stream, xi, (ST*)r.out, (const char*)packed[nblocks - 1], mf, nullptr, nullptr, part8,
                                     nullptr, Tn, nwg, nit, eps, fbuf, (const char*)packed[nblocks - 1]);
   return MV_OK;
 }
@@ -826,7 +842,6 @@ extern "C" size_t mv_mrf_packed_bytes(int dtype) {
 }
 
 // tile geometry per storage type: bf16/f16: 8 waves x 64 steps; fp32 (split operands, 2x LDS): 8 x 16 or 4 x 32 steps
-static inline bool mrf_fp32_storage(int dtype) { return dtype == MV_F32 || dtype == MV_F32_W16; }
 static inline int mrf_tile_t(int dtype) { return dtype == MV_F32_W16 ? 4 * 1 * 16 : dtype == MV_F32 ? 8 * 1 * 16 : 8 * 4 * 16; }
 // f32w16 tile form (chains the streaming form does not take): 8 waves x 32 steps (the single-f16 weight image is 48 KB, so a
 // 256-step shared tile fits)
@@ -888,9 +903,55 @@ extern "C" int mv_mrf_block_fwd_cl(const void* x, void* out, const void* packed,
   return MV_OK;
 }
 
-extern "C" size_t mv_mrf_chain_workspace_bytes(int B, int T_, int dtype) {
-  const size_t es = mrf_fp32_storage(dtype) ? 4 : 2;
-  return 3 * mrf_act_bytes(B, T_, es) + (mv_mrf_workspace_bytes(B, T_, dtype) + 255) / 256 * 256 + (size_t)B * 128 * sizeof(float);
+extern "C" size_t mv_mrf_chain_workspace_bytes(int B, int T_, int dtype) { return mrf_chain_ws(B, T_, dtype).total; }
+
+// What both chain entries check and decode the same way, behind their own argument checks: pointers, alignment, one MrfMeta per block
+// and the MV_F32_W16P code.  The dtype itself is judged by mrf_chain_run's switch, after the dilations.
+static int mrf_chain_request(const void* x, void* out, const void* const* packed, const int* dilations, int nblocks, void* workspace,
+                             int B, int T_, float eps, int dtype, void* stream, MrfChainReq* r) {
+  MV_CHECK_ARG(x && packed && dilations && workspace && nblocks >= 1 && nblocks <= 8 && B > 0 && B <= 65535 && T_ > 0);
+  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)workspace & 255) == 0);
+  for (int i = 0; i < nblocks; ++i) {
+    MV_CHECK_ARG(packed[i] && ((uintptr_t)packed[i] & 15) == 0);
+    if (!mrf_make_meta(dilations + 3 * i, &r->metas[i])) return MV_ERR_UNSUPPORTED;
+  }
+  r->x = x; r->out = out; r->packed = packed; r->nblocks = nblocks; r->ws = (char*)workspace; r->B = B; r->T = T_; r->eps = eps;
+  r->x_pair_in = dtype == MV_F32_W16P;
+  r->dtype = r->x_pair_in ? MV_F32_W16 : dtype;
+  r->stream = (hipStream_t)stream;
+  return MV_OK;
+}
+
+// The one dispatcher of the chain: storage dtype -> form and tile geometry (see mrf_tile_t).  *tail is filled unless kind is MATERIALIZE.
+static int mrf_chain_run(const MrfChainReq& r, MrfChainKind kind, MrfChainTail* tail) {
+  const MrfChainWs lay = mrf_chain_ws(r.B, r.T, r.dtype);
+  int rc;
+  switch (r.dtype) {
+    case MV_F32:
+      // wide dilations (halo > 5) do not fit 160 KB next to the hi+lo weight images: 4 waves x 32 steps, same 128-step workgroup tile
+      rc = mrf_chain_launch<float, 8, 1>(r, lay, kind, tail);
+      if (rc == MV_ERR_UNSUPPORTED) rc = mrf_chain_launch<float, 4, 2>(r, lay, kind, tail);
+      break;
+    case MV_F32_W16: {
+      // every block with the dilations (1, 3, 5): the streaming form (mrf_stream.hip), else the tile form.  The streaming form has no
+      // affine kernel (its tail goes to a consumer that takes the partial sums), and it alone reads pair-row input.
+      bool all_std = true;
+      for (int i = 0; i < r.nblocks; ++i) all_std = all_std && mrf_meta_is_std(r.metas[i]);
+      if (all_std && kind != TAIL_WITH_AB) {
+        rc = mvi_mrf_chain_stream(r.x, r.out, r.packed, r.nblocks, r.ws, lay, r.B, r.T, r.eps, r.stream, r.x_pair_in, tail);
+        if (rc != MV_ERR_UNSUPPORTED) break;
+      }
+      if (r.x_pair_in) return MV_ERR_UNSUPPORTED;
+      rc = mrf_chain_launch<f32w16, 8, 2>(r, lay, kind, tail);
+      break;
+    }
+    case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(r, lay, kind, tail); break;
+    case MV_F16: rc = mrf_chain_launch<f16, 8, 4>(r, lay, kind, tail); break;
+    default: return MV_ERR_DTYPE;
+  }
+  if (rc != MV_OK) return rc;
+  MV_LAUNCH_CHECK();
+  return MV_OK;
 }
 
 // chain + the generator's output projection (Conv1d(64,1,ks,pad ks/2) + activation): the last block's output is formed inside the
@@ -898,110 +959,32 @@ extern "C" size_t mv_mrf_chain_workspace_bytes(int B, int T_, int dtype) {
 extern "C" int mv_mrf_chain_out_fwd_cl(const void* x, void* wave, const void* const* packed, const int* dilations, int nblocks,
                                        void* workspace, const void* conv_packed, float conv_bias, int ks, int act, int B, int T_,
                                        float eps, int dtype, void* stream) {
-  MV_CHECK_ARG(x && wave && packed && dilations && workspace && conv_packed && nblocks >= 1 && nblocks <= 8 && B > 0 && B <= 65535 && T_ > 0);
-  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)workspace & 255) == 0 && ks > 0 && (ks & 1));
-  const int x_pair_in = dtype == MV_F32_W16P;                          // x arrives as pair rows (streaming form only)
-  if (x_pair_in) dtype = MV_F32_W16;
-  MrfMeta metas[8];
-  for (int i = 0; i < nblocks; ++i) {
-    MV_CHECK_ARG(packed[i] && ((uintptr_t)packed[i] & 15) == 0);
-    if (!mrf_make_meta(dilations + 3 * i, &metas[i])) return MV_ERR_UNSUPPORTED;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const size_t es = mrf_fp32_storage(dtype) ? 4 : 2;
-  float* ab = reinterpret_cast<float*>(ws + 3 * mrf_act_bytes(B, T_, es) + (mv_mrf_workspace_bytes(B, T_, dtype) + 255) / 256 * 256);
-  const void* fl = nullptr;
-  const void* xl_ = nullptr;
-  int rc;
-  const int cdt = dtype == MV_F32_W16 ? MV_F32 : dtype;                // the output conv sees fp32 rows either way
-  const bool fold = mvi_conv_out_affine_takes_partials(cdt, ks);     // the output conv forms the last block's affine itself: one launch less
-  const float* p8 = nullptr; const float* tb8 = nullptr; int nwg8 = 0, x_pair = 0;
-  bool all_std = true;
-  for (int i = 0; i < nblocks; ++i) all_std = all_std && mrf_meta_is_std(metas[i]);
-  switch (dtype) {
-    case MV_F32:
-      rc = mrf_chain_launch<float, 8, 1>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_, fold ? &p8 : nullptr, &tb8, &nwg8);
-      if (rc == MV_ERR_UNSUPPORTED)
-        rc = mrf_chain_launch<float, 4, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_, fold ? &p8 : nullptr, &tb8, &nwg8);
-      break;
-    case MV_F32_W16: {
-      if (fold && all_std) {     // streaming form (mrf_stream.hip)
-        rc = mvi_mrf_chain_stream(x, nullptr, packed, nblocks, ws, mrf_act_bytes(B, T_, 4), B, T_, eps, st, &fl, &xl_, &x_pair, &p8, &tb8, &nwg8, x_pair_in);
-        if (rc != MV_ERR_UNSUPPORTED) break;
-      }
-      if (x_pair_in) return MV_ERR_UNSUPPORTED;      // (the tile form reads fp32 rows)
-      rc = mrf_chain_launch<f32w16, 8, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_, fold ? &p8 : nullptr, &tb8, &nwg8);
-      break;
-    }
-    case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_); break;
-    case MV_F16: rc = mrf_chain_launch<f16, 8, 4>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab, &fl, &xl_); break;
-    default: return MV_ERR_DTYPE;
-  }
+  MV_CHECK_ARG(wave && conv_packed && ks > 0 && (ks & 1));
+  MrfChainReq r;
+  int rc = mrf_chain_request(x, nullptr, packed, dilations, nblocks, workspace, B, T_, eps, dtype, stream, &r);
   if (rc != MV_OK) return rc;
-  MV_LAUNCH_CHECK();
+  const int cdt = r.dtype == MV_F32_W16 ? MV_F32 : r.dtype;          // the output conv sees fp32 storage either way
+  // the output conv forms the last block's affine itself where it can: one launch less
+  const MrfChainKind kind = mvi_conv_out_affine_takes_partials(cdt, ks) ? TAIL_WITH_PARTIALS : TAIL_WITH_AB;
+  MrfChainTail tail;
+  rc = mrf_chain_run(r, kind, &tail);
+  if (rc != MV_OK) return rc;
   // conv_packed = mv_conv_out_pack_all image: the fp32 [ks][64] weights come first
-  rc = mvi_conv_out_affine(fl, xl_, ab, (const float*)conv_packed, conv_bias, wave, B, T_, MRF_C, ks, ks / 2, act, cdt, st, p8, tb8, nwg8, eps, x_pair);
+  const float* ab = reinterpret_cast<const float*>(r.ws + mrf_chain_ws(B, T_, r.dtype).ab);
+  rc = mvi_conv_out_affine(tail, ab, (const float*)conv_packed, conv_bias, wave, B, T_, MRF_C, ks, ks / 2, act, cdt, eps, r.stream);
   if (rc != MV_OK) return rc;
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
 
+// out == NULL: the chain's passes run and leave (f, x, partial sums) in the workspace, nothing is materialised (bench.py times the
+// passes the generator really runs this way: its last block's output is formed inside the output conv)
 extern "C" int mv_mrf_chain_fwd_cl(const void* x, void* out, const void* const* packed, const int* dilations, int nblocks,
                                    void* workspace, int B, int T_, float eps, int dtype, void* stream) {
-  MV_CHECK_ARG(x && packed && dilations && workspace && nblocks >= 1 && nblocks <= 8 && B > 0 && B <= 65535 && T_ > 0);
-  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)workspace & 255) == 0);
-  const int x_pair_in = dtype == MV_F32_W16P;                          // x arrives as pair rows (streaming form only)
-  if (x_pair_in) dtype = MV_F32_W16;
-  MrfMeta metas[8];
-  for (int i = 0; i < nblocks; ++i) {
-    MV_CHECK_ARG(packed[i] && ((uintptr_t)packed[i] & 15) == 0);
-    if (!mrf_make_meta(dilations + 3 * i, &metas[i])) return MV_ERR_UNSUPPORTED;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  int rc;
-  // out == NULL: the chain's passes run and leave (f, x, partial sums) in the workspace, nothing is materialised (bench.py times the
-  // passes the generator really runs this way: its last block's output is formed inside the output conv)
-  float ab_dummy[1]; const void* fl_ = nullptr; const void* xl2_ = nullptr; const float* p8_ = nullptr; const float* tb_ = nullptr; int nw_ = 0;
-  if (!out && dtype != MV_F32_W16) {
-    switch (dtype) {
-      case MV_F32:
-        rc = mrf_chain_launch<float, 8, 1>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_);
-        if (rc == MV_ERR_UNSUPPORTED)
-          rc = mrf_chain_launch<float, 4, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_);
-        break;
-      case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_); break;
-      case MV_F16: rc = mrf_chain_launch<f16, 8, 4>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_); break;
-      default: return MV_ERR_DTYPE;
-    }
-    if (rc != MV_OK) return rc;
-    MV_LAUNCH_CHECK();
-    return MV_OK;
-  }
-  switch (dtype) {
-    case MV_F32:
-      rc = mrf_chain_launch<float, 8, 1>(x, out, packed, metas, nblocks, ws, B, T_, eps, st);
-      if (rc == MV_ERR_UNSUPPORTED) rc = mrf_chain_launch<float, 4, 2>(x, out, packed, metas, nblocks, ws, B, T_, eps, st);
-      break;
-    case MV_F32_W16: {
-      bool all_std = true;
-      for (int i = 0; i < nblocks; ++i) all_std = all_std && mrf_meta_is_std(metas[i]);
-      if (all_std) {
-        const void* fl = nullptr; const void* xl_ = nullptr; int xp = 0, nw = 0; const float* p8 = nullptr; const float* tb = nullptr;
-        rc = mvi_mrf_chain_stream(x, out, packed, nblocks, ws, mrf_act_bytes(B, T_, 4), B, T_, eps, st, &fl, &xl_, &xp, &p8, &tb, &nw, x_pair_in);
-        if (rc != MV_ERR_UNSUPPORTED) break;
-      }
-      if (x_pair_in) return MV_ERR_UNSUPPORTED;
-      rc = out ? mrf_chain_launch<f32w16, 8, 2>(x, out, packed, metas, nblocks, ws, B, T_, eps, st)
-               : mrf_chain_launch<f32w16, 8, 2>(x, nullptr, packed, metas, nblocks, ws, B, T_, eps, st, ab_dummy, &fl_, &xl2_, &p8_, &tb_, &nw_);
-      break;
-    }
-    case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(x, out, packed, metas, nblocks, ws, B, T_, eps, st); break;
-    case MV_F16: rc = mrf_chain_launch<f16, 8, 4>(x, out, packed, metas, nblocks, ws, B, T_, eps, st); break;
-    default: return MV_ERR_DTYPE;
-  }
+  MV_CHECK_ARG(((uintptr_t)out & 15) == 0);
+  MrfChainReq r;
+  const int rc = mrf_chain_request(x, out, packed, dilations, nblocks, workspace, B, T_, eps, dtype, stream, &r);
   if (rc != MV_OK) return rc;
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  MrfChainTail tail;
+  return mrf_chain_run(r, out ? MATERIALIZE : PASSES_ONLY, &tail);
 }

@@ -33,10 +33,9 @@ constexpr int SR_WB_ALL = (MRF_CONV_FRAGS + MRF_RES_FRAGS + MRF_FUS_FRAGS) * FRA
 constexpr int SR_WB_CONV = MRF_CONV_FRAGS * FRAG_BYTES;
 constexpr int SR_ROWB = 256;                // bytes of one row in HBM (fp32 [64] or pair)
 
-// f as hl8 rows as well: measured at C2 it costs more than it saves - the encode (cvt, residual, clamp, cvt: ~5 VALU per value) lands
-// in the matrix-bound F passes (+1.3 us each, F0 +3.1) while the A passes and the output conv, which read f, are not bound by bytes any
-// more once x' is 192 bytes (A 37 -> 33 us either way).  The code paths stay (final kernel, output conv, tests of the format).
-constexpr bool SR_FHL = false;
+// f stays fp32 rows in every form.  As hl8 rows, measured at C2, it costs more than it saves: the encode (cvt, residual, clamp, cvt:
+// ~5 VALU per value) lands in the matrix-bound F passes (+1.3 us each, F0 +3.1) while the A passes and the output conv, which read f,
+// are not bound by bytes any more once x' is 192 bytes (A 37 -> 33 us either way).  That variant is no longer in the tree.
 enum { SM_V0 = 0, SM_F0 = 1, SM_A = 2, SM_F = 3 };
 // V0: fp32 rows -> statistics of v.   F0: fp32 rows -> f (fp32) + statistics of f.   F: pair rows (LDS-DMA) -> the same.
 // A : f_prev (fp32), x_prev (fp32 or pair rows) -> x' = a f + b + x as pair rows (written once) + statistics of v'.
@@ -55,9 +54,9 @@ struct SrArgs {
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-// HL: the streams between the blocks (x' and f) are hl8 rows (mfma.h) instead of pair / fp32 rows.  Then F0 writes f as hl8, A reads
-// f as hl8 and x as fp32 rows (XPAIR false: block 1) or hl8 rows (XPAIR true) and writes x' as hl8, F reads x' through registers
-// (hi plane = the operand image's hi halves as they are, lo bytes widened to f16) and writes f as hl8.  V0 is not affected.
+// HL: the residual stream x' between the blocks is hl8 rows (mfma.h) instead of pair rows.  Then A reads x as fp32 rows (XPAIR false:
+// block 1) or hl8 rows (XPAIR true) and writes x' as hl8, F reads x' through registers (hi plane = the operand image's hi halves as they
+// are, lo bytes widened to f16).  f is fp32 rows either way, and V0 is not affected.
 template <int MODE, bool XPAIR, bool HL>
 __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
   using M = Mma<f32w16>;
@@ -66,9 +65,8 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
   constexpr bool FULL = (MODE == SM_F0 || MODE == SM_F);
   constexpr bool DMA = ((MODE == SM_F) && !HL) || (MODE == SM_V0 && XPAIR);     // pair rows in HBM ARE the LDS operand image
   constexpr bool XHL = HL && (MODE == SM_F || (MODE == SM_A && XPAIR));          // x arrives as hl8 rows
-  constexpr bool FHL = HL && SR_FHL;                                             // f as hl8 rows too (off: see SR_FHL)
   constexpr int XRB = XHL ? SR_HLB : SR_ROWB;                                    // row bytes of x (in), of f (in or out), of x' (out)
-  constexpr int FRB = FHL ? SR_HLB : SR_ROWB;
+  constexpr int FRB = SR_ROWB;
   constexpr int ORB = HL ? SR_HLB : SR_ROWB;
   constexpr bool NEED5 = FULL, NEED8 = (MODE == SM_A);
   constexpr int WLB = FULL ? SR_WB_ALL : SR_WB_CONV;
@@ -207,15 +205,9 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
         sx1[it] = __builtin_amdgcn_raw_buffer_load_b128(rx, off + 16, 0, 0);
       }
       if constexpr (MODE == SM_A) {
-        if constexpr (FHL) {
-          sf0[it] = __builtin_amdgcn_raw_buffer_load_b128(rf, t * SR_HLB + cg * 16, 0, 0);
-          const u32x2 l = __builtin_amdgcn_raw_buffer_load_b64(rf, t * SR_HLB + 128 + cg * 8, 0, 0);
-          sf1[it] = u32x4{l[0], l[1], 0u, 0u};
-        } else {
-          const int off = t * SR_ROWB + cg * 32;
-          sf0[it] = __builtin_amdgcn_raw_buffer_load_b128(rf, off, 0, 0);
-          sf1[it] = __builtin_amdgcn_raw_buffer_load_b128(rf, off + 16, 0, 0);
-        }
+        const int off = t * SR_ROWB + cg * 32;
+        sf0[it] = __builtin_amdgcn_raw_buffer_load_b128(rf, off, 0, 0);
+        sf1[it] = __builtin_amdgcn_raw_buffer_load_b128(rf, off + 16, 0, 0);
       }
     }
   };
@@ -244,13 +236,9 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { xv[e] = p[e]; xv[4 + e] = q[e]; }
           }
-          if constexpr (FHL) {
-            hl8_decode(sf0[it], u32x2{sf1[it][0], sf1[it][1]}, fv);
-          } else {
-            const f32x4 fp = __builtin_bit_cast(f32x4, sf0[it]), fq = __builtin_bit_cast(f32x4, sf1[it]);
+          const f32x4 fp = __builtin_bit_cast(f32x4, sf0[it]), fq = __builtin_bit_cast(f32x4, sf1[it]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { fv[e] = fp[e]; fv[4 + e] = fq[e]; }
-          }
+          for (int e = 0; e < 4; ++e) { fv[e] = fp[e]; fv[4 + e] = fq[e]; }
           const bool inside = t >= 0 && t < Tn;        // rows outside the sample are the conv's zero padding, not b
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = inside ? ra[e] * fv[e] + rb[e] + xv[e] : 0.f;
@@ -470,22 +458,9 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float q = ok ? f[m][r] : 0.f; s1[m] += q; s2[m] += q * q; }
         }
-        if constexpr (FHL) {          // this lane's 4 channels of M-tile m: 8 bytes of the hi plane, 4 of the lo plane
-          const int vo = (t0 + col) * SR_HLB;
+        const int vo = (t0 + col) * SR_ROWB + 16 * g;
 #pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            const uint32_t h0 = pack_f16(f[m][0], f[m][1]), h1 = pack_f16(f[m][2], f[m][3]);
-            const f16x2_t a0 = __builtin_bit_cast(f16x2_t, h0), a1 = __builtin_bit_cast(f16x2_t, h1);
-            const uint32_t l4 = hl8_pack4((f[m][0] - (float)a0[0]) * SR_LOS, (f[m][1] - (float)a0[1]) * SR_LOS,
-                                          (f[m][2] - (float)a1[0]) * SR_LOS, (f[m][3] - (float)a1[1]) * SR_LOS);
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{h0, h1}, ro, vo + 32 * m + 8 * g, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(l4, ro, vo + 128 + 16 * m + 4 * g, 0, 0);
-          }
-        } else {
-          const int vo = (t0 + col) * SR_ROWB + 16 * g;
-#pragma unroll
-          for (int m = 0; m < 4; ++m) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f[m]), ro, vo + 64 * m, 0, 0);
-        }
+        for (int m = 0; m < 4; ++m) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f[m]), ro, vo + 64 * m, 0, 0);
       }
     };
     auto finish_only = [&]() {
@@ -589,7 +564,7 @@ __global__ __launch_bounds__(SR_NW * 64) void mrf_stream_kernel(SrArgs a) {
 }
 
 // the chain's materialised output (mv_mrf_chain_fwd_cl): out = a f + b + x as fp32 rows; x fp32 or pair rows
-template <bool XPAIR, bool HL>      // HL: f is hl8 rows, and so is x when XPAIR
+template <bool XPAIR, bool HL>      // x: fp32 rows, pair rows (XPAIR) or hl8 rows (XPAIR && HL); f: fp32 rows
 __global__ __launch_bounds__(256) void mrf_stream_final_kernel(const float* __restrict__ f, const void* __restrict__ x,
                                                                const float* __restrict__ part8, const float* __restrict__ tab,
                                                                float* __restrict__ out, int Tn, int nwg, float eps) {
@@ -629,18 +604,8 @@ __global__ __launch_bounds__(256) void mrf_stream_final_kernel(const float* __re
 #pragma unroll
       for (int e = 0; e < 4; ++e) { xv[e] = u[e]; xv[4 + e] = w[e]; }
     }
-    f32x4 fu, fw;
-    if constexpr (HL && SR_FHL) {
-      const char* p = reinterpret_cast<const char*>(f) + ((size_t)b * Tn + t) * SR_HLB;
-      float fv[8];
-      hl8_decode(*reinterpret_cast<const u32x4*>(p + cg * 16), *reinterpret_cast<const u32x2*>(p + 128 + cg * 8), fv);
-      fu = f32x4{fv[0], fv[1], fv[2], fv[3]};
-      fw = f32x4{fv[4], fv[5], fv[6], fv[7]};
-    } else {
-      const float* fp = f + base + (size_t)t * 64 + cg * 8;
-      fu = *reinterpret_cast<const f32x4*>(fp);
-      fw = *reinterpret_cast<const f32x4*>(fp + 4);
-    }
+    const float* fp = f + base + (size_t)t * 64 + cg * 8;
+    const f32x4 fu = *reinterpret_cast<const f32x4*>(fp), fw = *reinterpret_cast<const f32x4*>(fp + 4);
     f32x4 o0, o1;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -677,22 +642,21 @@ static void sr_launch(const SrArgs& a, int B, hipStream_t stream) {
 using namespace mv;
 
 // internal entry (mrf_fused.hip): the whole chain in the streaming form.  packed[i] = MV_F16 image of block i, every block with the
-// dilations (1, 3, 5).  ws: 3 activation buffers + partial sums (mv_mrf_chain_workspace_bytes).  out != nullptr: fp32 rows of the last
-// block's output are written; otherwise the caller gets (f_last, x_last, x_last_pair, part8, tab, nwg) for the fused output conv.
-int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, int nblocks, char* ws, size_t act_bytes, int B, int Tn,
-                         float eps, hipStream_t stream, const void** f_last, const void** x_last, int* x_last_pair,
-                         const float** part8_last, const float** tab_last, int* nwg_last, int x_pair_in) {
+// dilations (1, 3, 5).  ws / lay: the chain's workspace and its layout (mrf_chain_ws).  out != nullptr: fp32 rows of the last block's
+// output are written; otherwise *tail is filled for the fused output conv.
+int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, int nblocks, char* ws, const MrfChainWs& lay, int B, int Tn,
+                         float eps, hipStream_t stream, bool x_pair_in, MrfChainTail* tail) {
   if ((size_t)Tn * SR_ROWB >= (1ull << 31)) return MV_ERR_UNSUPPORTED;     // 32-bit buffer offsets
   int L, nwg;
   sr_geometry(B, Tn, &L, &nwg);
-  float* fbuf = reinterpret_cast<float*>(ws);
-  char* xbuf[2] = {ws + act_bytes, ws + 2 * act_bytes};
-  float* part5 = reinterpret_cast<float*>(ws + 3 * act_bytes);
+  float* fbuf = reinterpret_cast<float*>(ws + lay.f);
+  char* xbuf[2] = {ws + lay.x[0], ws + lay.x[1]};
+  float* part5 = reinterpret_cast<float*>(ws + lay.part5);
   float* part8 = part5 + (size_t)B * nwg * 32;
   SrArgs a{};
   a.Tn = Tn; a.L = L; a.nwg = nwg; a.eps = eps;
   const void* xi = x;
-  bool xi_pair = x_pair_in != 0;               // the producer already wrote pair rows (the last upsampler's streaming kernel)
+  bool xi_pair = x_pair_in;                    // the producer already wrote pair rows (the last upsampler's streaming kernel)
   const bool hl = !xi_pair;                   // hl8 rows between the blocks (pair-row input keeps pair rows)
   for (int i = 0; i < nblocks; ++i) {
     a.packed = (const char*)packed[i];
@@ -727,9 +691,7 @@ int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, in
       hipLaunchKernelGGL((mrf_stream_final_kernel<true, false>), dim3(gx, B), dim3(256), 0, stream, fbuf, xi, part8, tabp, (float*)out, Tn, nwg, eps);
     return MV_OK;
   }
-  // x_last_pair: 0 = x and f fp32 rows, 1 = x pair rows, 2 = x and f hl8 rows, 3 = x fp32 with f hl8 (one-block chain), 4 = x hl8, f fp32
-  *f_last = fbuf; *x_last = xi;
-  *x_last_pair = !hl ? 1 : SR_FHL ? (xi_pair ? 2 : 3) : (xi_pair ? 4 : 0);
-  *part8_last = part8; *tab_last = tabp; *nwg_last = nwg;
+  // pair-row input keeps pair rows; otherwise x' is hl8 rows, and a one-block chain hands on the fp32 rows it was given
+  *tail = MrfChainTail{fbuf, xi, !hl ? MRF_ROWS_PAIR : xi_pair ? MRF_ROWS_HL8 : MRF_ROWS_FP32, part8, tabp, nwg};
   return MV_OK;
 }

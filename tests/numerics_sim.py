@@ -184,12 +184,12 @@ def logmel_like(B, T, seed=0):
     return O.mel_spectrogram(wave).float().contiguous()
 
 
-def mrf_blocks(seed=0):
+def mrf_blocks(seed=0, dilations=(1, 3, 5)):
     """Three seeded 64-channel MultiReceptiveFieldBlocks with non-trivial GroupNorm affines and biases, on the CPU, and their state
     dicts - the blocks of the chain tests (tests/test_gpu_mrf_stream.py, tests/test_gpu_inference_off_unit_scale.py)."""
     import hifigan_modified as H
     torch.manual_seed(seed)
-    blks = [H.MultiReceptiveFieldBlock(64, 64) for _ in range(3)]
+    blks = [H.MultiReceptiveFieldBlock(64, 64, dilations=list(dilations)) for _ in range(3)]
     for bk in blks:
         for p in bk.parameters():
             if p.dim() == 1 and p.numel() in (20, 64):

@@ -55,6 +55,48 @@ def test_stream_chain_vs_oracle_ragged(H, B, T):
             assert O.rel_l2(y.cpu(), full.cpu()) < 4e-4
 
 
+@pytest.mark.parametrize("arm", ["tile_form", "ks17"])
+def test_w16_chain_arms_beside_the_streaming_form(H, arm):
+    """The two arms of the chain's dispatcher (csrc/mrf_fused.hip, mrf_chain_run) that no other test reaches in the two-product mode,
+    at B = 2, T = 200 (ragged against every tile width), two blocks, against the fp64 oracle:
+      tile_form  dilations (1, 2, 4): not the streaming form's (1, 3, 5), so mv_mrf_chain_fwd_cl runs mrf_kernel<f32w16> and its pass F;
+      ks17       mv_mrf_chain_out_fwd_cl with a 17-tap output conv: beyond the 16 MFMA rows of the form that takes the last block's
+                 partial sums, so the chain runs in its tile form, mrf_affine_kernel writes the deferred affine and the fp32 VALU
+                 output conv applies it.  The head is linear here (ACT_NONE): what is compared is the chain's output seen through an
+                 fp32 conv (its own rounding: 2^-24 per term), not a saturated tanh.
+    Bound: the 4e-4 of test_stream_chain_vs_oracle_ragged, the existing test of this storage mode (single-f16 weights: ~1.5e-4 per
+    block); the tile form keeps fp32 rows between the blocks, so it has no rounding the streaming form lacks."""
+    import ctypes
+    import torch.nn.functional as F
+    from hifigan_modified import _native as N, ops
+    from hifigan_modified.fused import MrfChain, mrf_fused_for
+    dil = (1, 2, 4) if arm == "tile_form" else (1, 3, 5)
+    blks, sds = mrf_blocks(0, dilations=dil)
+    chain = MrfChain([mrf_fused_for(bk.cuda().train(False)) for bk in blks[:2]])
+    torch.manual_seed(200)
+    x = torch.randn(2, 64, 200)
+    xc = x.cuda().transpose(1, 2).contiguous()
+    with torch.no_grad():
+        ref = x.double()
+        for sd in sds[:2]:
+            ref = O.mrf_block(ref, {k: v.double() for k, v in sd.items()}, "", dilations=dil)
+        if arm == "tile_form":
+            y = chain.forward_cl(xc, 2, w16=True)
+            assert torch.equal(y, chain.forward_cl(xc, 2, w16=True))
+            got = y.transpose(1, 2).cpu()
+        else:
+            torch.manual_seed(3)
+            w = (torch.randn(1, 64, 17) * (2.0 / 17) ** 0.5).cuda()
+            wt = torch.empty(N.lib().mv_conv_out_packed_bytes(64, 17), device="cuda", dtype=torch.uint8)
+            N.call("mv_conv_out_pack_all", ctypes.c_void_p(w.data_ptr()), ops._DT[w.dtype], ctypes.c_void_p(wt.data_ptr()), 64, 17, ops._stream())
+            got = chain.forward_out_cl(xc, wt, 0.25, 17, N.ACT_NONE, w16=True).cpu()
+            assert got.shape == (2, 1, 200)
+            ref = F.conv1d(ref, w.cpu().double(), torch.tensor([0.25], dtype=torch.float64), padding=8)
+    e = O.rel_l2(got, ref)
+    print(f"[w16-arms] {arm}: rel-L2 vs fp64 oracle {e:.3e}")
+    assert e < 4e-4, (arm, e)
+
+
 def test_full_c2_batch_mixed_w16_meets_north_star(H):
     """bench.py's headline mode at BASELINE configs[1]'s full size: fp16 storage through up1, fp32 storage behind it, the three MRF
     blocks with two-product operands (streaming chain + fused output conv).  Four of the 32 clips against the oracle within

@@ -190,6 +190,82 @@ __global__ __launch_bounds__(256) void scale_to_kernel(const T* __restrict__ x, 
     st<T>(y + i, ld<T>(x + i) * f);
 }
 
+// ------------------------------------------------------------------------------------------- feature matching over hidden maps
+// Defined by this build: complete_vocoder.py:118,127 take the L1 of the discriminators' outputs only; these two
+// kernels extend that term to every hidden feature map, which lives in the stack's channels-last buffers (disc_fused.py).
+// 16 bytes of T <-> floats (p 16-byte aligned)
+template <typename T> __device__ __forceinline__ void ld16(const T* p, float* o) {
+  constexpr int V = 16 / (int)sizeof(T);
+  alignas(16) T tmp[V];
+  *reinterpret_cast<uint4*>(tmp) = *reinterpret_cast<const uint4*>(p);
+#pragma unroll
+  for (int e = 0; e < V; ++e) o[e] = ld<T>(tmp + e);
+}
+template <typename T> __device__ __forceinline__ void st16(T* p, const float* v) {
+  constexpr int V = 16 / (int)sizeof(T);
+  alignas(16) T tmp[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) st<T>(tmp + e, v[e]);
+  *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(tmp);
+}
+
+// acc[0] += scale * sum |a - b|.  loss_kernel's shape: 16-byte loads, fp32 partial sums, wave and workgroup reduction, one atomicAdd
+// per workgroup.  A thread keeps one accumulator per component of its load (V = 4 or 8 independent chains of
+// ceil(nvec / (grid * 256)) terms each) and folds them pairwise; the first nvec * V elements go through the vector loop (nvec = 0
+// when a pointer is not 16-byte aligned), the rest through the scalar one.
+template <typename T>
+__global__ __launch_bounds__(256) void fm_l1_kernel(const T* __restrict__ a, const T* __restrict__ b, long n, long nvec, float scale,
+                                                    float* __restrict__ acc) {
+  constexpr int V = 16 / (int)sizeof(T);
+  __shared__ float red[32];
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  float s[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) s[e] = 0.f;
+  for (long i = tid; i < nvec; i += stride) {
+    float av[V], bv[V];
+    ld16<T>(a + i * V, av);
+    ld16<T>(b + i * V, bv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) s[e] += fabsf(av[e] - bv[e]);
+  }
+#pragma unroll
+  for (int w = V / 2; w > 0; w >>= 1)
+#pragma unroll
+    for (int e = 0; e < w; ++e) s[e] += s[e + w];
+  float t = s[0];
+  for (long i = nvec * V + tid; i < n; i += stride) t += fabsf(ld<T>(a + i) - ld<T>(b + i));
+  t = block_sum(t, red);
+  if (threadIdx.x == 0) atomicAdd(acc, t * scale);
+}
+
+// g += c * sign(af - ar) * LeakyReLU'(af), c = coef * upstream[0]: the gradient of c * sum |af - ar| with respect to the
+// PRE-activation of af, added to the gradient the data-gradient conv left there.  LeakyReLU'(af) = (af >= 0 ? 1 : slope), the
+// convention of that conv's epilogue (disc_fused.hip: `svals[e] >= 0.f ? g : g * slope`); sign(0) = 0 as in F.l1_loss.  fp32
+// arithmetic with one rounding to T: the two possible magnitudes c and c * slope are formed once (__fmul_rn: never contracted into
+// the add), so an element is g, g + m or g - m.
+template <typename T>
+__global__ __launch_bounds__(256) void fm_inject_kernel(T* __restrict__ g, const T* __restrict__ af, const T* __restrict__ ar, long n,
+                                                        long nvec, const float* __restrict__ upstream, float coef, float slope) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const float c = __fmul_rn(coef, upstream[0]), cs = __fmul_rn(c, slope);
+  auto one = [&](float gv, float f, float r) {
+    const float m = f >= 0.f ? c : cs;
+    return f > r ? gv + m : (f < r ? gv - m : gv);
+  };
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  for (long i = tid; i < nvec; i += stride) {
+    float gv[V], fv[V], rv[V];
+    ld16<T>(g + i * V, gv);
+    ld16<T>(af + i * V, fv);
+    ld16<T>(ar + i * V, rv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) gv[e] = one(gv[e], fv[e], rv[e]);
+    st16<T>(g + i * V, gv);
+  }
+  for (long i = nvec * V + tid; i < n; i += stride) st<T>(g + i, one(ld<T>(g + i), ld<T>(af + i), ld<T>(ar + i)));
+}
+
 // ------------------------------------------------------------------------------------------- AdamW on a flat fp32 arena
 // one element of torch.optim.AdamW: decoupled weight decay, the two moments, the bias-corrected step
 __device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float wd,
@@ -534,6 +610,35 @@ extern "C" int mv_scale_to(const void* x, void* y, const float* factor_dev, floa
   MV_CHECK_ARG(x && y && n > 0);
   MV_DISPATCH(dtype, hipLaunchKernelGGL(scale_to_kernel<T>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y,
                                         factor_dev, factor, n));
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+// elements of T that go through 16-byte accesses: all whole groups when every pointer is 16-byte aligned, none otherwise
+template <typename T> static long fm_nvec(long n, const void* a, const void* b, const void* c) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) ? 0 : n / (16 / (long)sizeof(T));
+}
+
+extern "C" int mv_fm_l1(const void* a, const void* b, long n, float scale, float* acc, int dtype, void* stream) {
+  MV_CHECK_ARG(a && b && acc && n > 0);
+  // at most 1024 workgroups: the atomics on acc form a chain of that many fp32 additions at the most
+  MV_DISPATCH(dtype, {
+    const long nvec = fm_nvec<T>(n, a, b, nullptr);
+    hipLaunchKernelGGL(fm_l1_kernel<T>, dim3(grid_for(nvec ? nvec : n, 256, 1024)), dim3(256), 0, (hipStream_t)stream, (const T*)a,
+                       (const T*)b, n, nvec, scale, acc);
+  });
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_fm_inject(void* g, const void* af, const void* ar, long n, const float* upstream_dev, float coef, float slope,
+                            int dtype, void* stream) {
+  MV_CHECK_ARG(g && af && ar && upstream_dev && n > 0 && g != af && g != ar);
+  MV_DISPATCH(dtype, {
+    const long nvec = fm_nvec<T>(n, g, af, ar);
+    hipLaunchKernelGGL(fm_inject_kernel<T>, dim3(grid_for(nvec ? nvec : n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, (T*)g,
+                       (const T*)af, (const T*)ar, n, nvec, upstream_dev, coef, slope);
+  });
   MV_LAUNCH_CHECK();
   return MV_OK;
 }

@@ -8,7 +8,8 @@ Differences, all documented in DESIGN.md: the generator is the one ``conditioned
 §A; the reference's current-source generator does not construct); the embedding extractor (``embedding_extractors.py``)
 runs frozen (eval statistics, no gradient) with its one broken layer resized, see that module; the mel term is a real log-mel/STFT L1
 (``mel_mode="stft"``) instead of the reference's ``generated_mel = mel`` placeholder (``mel_mode="placeholder"``
-reproduces that: the term is then identically zero).
+reproduces that: the term is then identically zero); `fm_mode="features"` (opt-in) extends the reference's
+output-only "feature matching" L1 to every hidden feature map of every sub-discriminator, HiFi-GAN's definition of the term.
 """
 from __future__ import annotations
 
@@ -25,7 +26,12 @@ from .generator import ModifiedHiFiGANGenerator
 from .mel import mel_filterbank
 
 
+FM_MODES = ("output", "features")
+
+
 class ModifiedHiFiGANVocoder(nn.Module):
+    fm_mode = "output"          # host state, not a parameter or buffer: set_feature_matching; the trainer's checkpoint stores it
+
     def __init__(self, input_channels: int = 80, hidden_channels: int = 512,
                  speaker_embedding_dim: int = 192, emotion_embedding_dim: int = 256,
                  sample_rate: int = 22050, n_fft: int = 1024, hop: Optional[int] = None, **generator_kwargs):
@@ -53,6 +59,15 @@ class ModifiedHiFiGANVocoder(nn.Module):
         wave = self.generator(mel_spectrogram, speaker_embedding, emotion_embedding)
         return {"generated_waveform": wave, "speaker_embedding": speaker_embedding, "emotion_embedding": emotion_embedding}
 
+    def set_feature_matching(self, mode: str):
+        """"output" (the default): the reference's term, L1 between the discriminators' final outputs (complete_vocoder.py:118,127).
+        "features": per sub-discriminator that L1 plus sum_l mean|a_l(fake) - a_l(real).detach()| over its four hidden feature maps
+        (a_l: hidden conv l after its LeakyReLU; each mean over all elements of the map, the MPD fold's zero padding included)."""
+        if mode not in FM_MODES:
+            raise ValueError(f"feature-matching mode must be one of {FM_MODES}, got {mode!r}")
+        self.fm_mode = mode
+        return self
+
     def get_discriminator_outputs(self, real_audio, fake_audio):
         return self.discriminators(real_audio, fake_audio)
 
@@ -65,13 +80,22 @@ class ModifiedHiFiGANVocoder(nn.Module):
         """generated_mel tensor -> L1(generated_mel, mel_spectrogram) like the reference; None -> the mel of
         `fake_audio` is taken by the STFT kernel and compared with `mel_spectrogram` (a log-mel target)."""
         D = self.discriminators
-        with torch.no_grad():               # D(real) only enters through .detach() (complete_vocoder.py:118,123)
-            mpd_real, msd_real = D.mpd(real_audio), D.msd(real_audio)
-        mpd_fake, msd_fake = D.mpd(fake_audio), D.msd(fake_audio)
+        if self.fm_mode == "features":
+            # the real pass keeps its hidden maps (no gradient), the fake pass adds their L1 per stack (forward_fm)
+            mpd_real, msd_real = D.mpd.features(real_audio), D.msd.features(real_audio)
+            mpd_pairs = D.mpd.forward_fm(fake_audio, mpd_real)
+            msd_pairs = D.msd.forward_fm(fake_audio, msd_real)
+            mpd_fake, msd_fake = [o for o, _ in mpd_pairs], [o for o, _ in msd_pairs]
+            mpd_fm = sum(Fn.l1(f, r) + h for (r, _), (f, h) in zip(mpd_real, mpd_pairs))
+            msd_fm = sum(Fn.l1(f, r) + h for (r, _), (f, h) in zip(msd_real, msd_pairs))
+        else:
+            with torch.no_grad():               # D(real) only enters through .detach() (complete_vocoder.py:118,123)
+                mpd_real, msd_real = D.mpd(real_audio), D.msd(real_audio)
+            mpd_fake, msd_fake = D.mpd(fake_audio), D.msd(fake_audio)
+            mpd_fm = sum(Fn.l1(f, r) for r, f in zip(mpd_real, mpd_fake))
+            msd_fm = sum(Fn.l1(f, r) for r, f in zip(msd_real, msd_fake))
         mpd_loss = sum(Fn.mse_const(f, 1.0) for f in mpd_fake)
         msd_loss = sum(Fn.mse_const(f, 1.0) for f in msd_fake)
-        mpd_fm = sum(Fn.l1(f, r) for r, f in zip(mpd_real, mpd_fake))
-        msd_fm = sum(Fn.l1(f, r) for r, f in zip(msd_real, msd_fake))
         if generated_mel is None:
             mel_loss = Fn.mel_l1(fake_audio, mel_spectrogram, self.mel_fb, self.n_fft, self.hop)
         else:
@@ -265,6 +289,8 @@ class VocoderTrainer:
         # one graph per (input signature, phase); with accumulation the phases are "accumulate" and "accumulate + step", each with its
         # own warm-up steps; the optimizers' state (runs, state block, step counts) belongs to the stepping phase only
         key = sig if self.accumulation_steps == 1 else sig + ("step" if do_step else "accumulate",)
+        if self.vocoder.fm_mode != "output":
+            key = key + (("fm", self.vocoder.fm_mode),)    # a mode change after a capture records its own graph
         st = self._graphs.get(key)
         if st is None:
             st = self._graphs[key] = {"warm": 0, "graph": None}
@@ -369,6 +395,8 @@ class VocoderTrainer:
             ck["dropout_rng_state"] = self.dropout_rng.state_dict()
         if self.schedulers:
             ck["scheduler_state_dicts"] = [s.state_dict() for s in self.schedulers]
+        if self.vocoder.fm_mode != "output":             # (a default trainer's file keeps the reference's keys)
+            ck["fm_mode"] = self.vocoder.fm_mode
         ck.update(self.window.checkpoint_extras())
         torch.save(ck, path)
 
@@ -381,4 +409,5 @@ class VocoderTrainer:
             self.dropout_rng.load_state_dict(ck["dropout_rng_state"])
         for sch, sd in zip(self.schedulers, ck.get("scheduler_state_dicts", ())):
             sch.load_state_dict(sd)
+        self.vocoder.set_feature_matching(ck.get("fm_mode", "output"))     # (no key: the reference's term)
         self.window.reset()                  # a checkpoint is always a window boundary

@@ -108,10 +108,30 @@ def _as4d(w):
     return w if w.dim() == 4 else w.unsqueeze(2)        # Conv1d [O,C,k] -> [O,C,1,k]
 
 
-class _DiscStack(Function):
+def _cl_buffers(feats):
+    """Logical [B,C,H,W] / [B,C,W] feature views (disc_features) -> their channels-last buffers; raises when a tensor is not such a view."""
+    bufs = []
+    for f in feats:
+        b = f.permute(0, 2, 3, 1) if f.dim() == 4 else f.permute(0, 2, 1)
+        if not b.is_contiguous():
+            raise ValueError("feature matching: the real features must be the channels-last views that disc_features returns")
+        bufs.append(b if f.dim() == 4 else b.unsqueeze(1))
+    return bufs
+
+
+def _logical(a, xdim):
+    """Channels-last buffer [B,H,W,C] -> the logical [B,C,H,W] (or [B,C,W]) view of it."""
+    return a.permute(0, 3, 1, 2) if xdim == 4 else a.view(a.shape[0], a.shape[2], a.shape[3]).permute(0, 2, 1)
+
+
+class _Stack:
+    """The one forward body and the one backward body of a discriminator stack.  `real` (optional): the real waveform's four hidden
+    feature maps as channels-last buffers - the forward then also returns fm = sum_l mean|a_l - real_l| (fp32, 0-dim) and the backward
+    adds that term's gradient to g right behind the data gradient that produces it (mv_fm_inject)."""
+
     @staticmethod
-    def forward(ctx, x0, slope, *params):
-        """x0 [B,1,H,W] (MPD fold) or [B,1,W] (MSD, pooled); params = w1,b1,...,w5,b5."""
+    def forward(ctx, x0, slope, params, real=None):
+        """x0 [B,1,H,W] (MPD fold) or [B,1,W] (MSD, pooled); params = w1,b1,...,w5,b5.  Returns (out, acts, fm or None)."""
         ws = [_as4d(p) for p in params[0::2]]
         bs = list(params[1::2])
         dt = x0.dtype
@@ -161,21 +181,40 @@ class _DiscStack(Function):
             N.call("mv_dconv_cl_fwd", _P(acts[-1]), _P(hp), _P(hb), None, _P(y32), B, H, W, C4, 32, kh, kw, 1, N.ACT_NONE, float(slope),
                    ops._dt(x0), st())
             N.call("mv_take_channel", _P(y32), _P(out), B * H * W, 32, 0, ops._dt(x0), st())
+        fm = None
+        if real is not None:
+            for a, r in zip(acts, real):
+                if r.shape != a.shape or r.dtype != a.dtype:
+                    raise ValueError(f"feature matching: real feature {tuple(r.shape)} {r.dtype} does not match the stack's "
+                                     f"{tuple(a.shape)} {a.dtype}")
+            fm = ops._scalars.take(dev)
+            for a, r in zip(acts, real):
+                ops.fm_l1(a, r, acc=fm)
+            fm = fm.view(())
         ctx.geom = (B, H, W, kh, kw, float(slope), x0.dim())
-        ctx.save_for_backward(x0, *acts, *params)
-        return out
+        ctx.save_for_backward(x0, *acts, *params, *(real or ()))
+        return out, acts, fm
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, gfm=None, first_param=2):
+        """Gradients (x0, *params).  gfm: the incoming gradient of fm (device scalar) - None skips the injection.  first_param: where
+        the parameters start among the Function's forward arguments (ctx.needs_input_grad)."""
         B, H, W, kh, kw, slope, xdim = ctx.geom
         saved = ctx.saved_tensors
-        x0, acts, params = saved[0], list(saved[1:5]), list(saved[5:])
+        x0, acts, params, real = saved[0], list(saved[1:5]), list(saved[5:15]), list(saved[15:])
+        if gfm is None:
+            real = []
+        else:
+            gfm = gfm.reshape(1).float()
+        inject = lambda g, l: ops.fm_inject(g, acts[l], real[l], gfm, slope) if real else g
+        if gy is None:                                     # only fm was used
+            gy = ops._zeros((B, 1, H, W) if xdim == 4 else (B, 1, W), device=x0.device, dtype=x0.dtype)
         ws = [_as4d(p) for p in params[0::2]]
         bs = list(params[1::2])
         dt, dev, st = x0.dtype, x0.device, ops._stream
         gy = gy.contiguous()
         need = ctx.needs_input_grad
-        need_w = any(need[2:])
+        need_w = any(need[first_param:])
         grads = [None] * 10
         f32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
         to = lambda g, p: (g.view(p.shape) if g.dtype == p.dtype else ops.cast(g.view(p.shape).contiguous(), p.dtype))
@@ -207,6 +246,7 @@ class _DiscStack(Function):
             hpf, _ = _packs.head_padded(params[8], bs[4], dt, 1)
             N.call("mv_dconv_cl_fwd", _P(g32), _P(hpf), None, _P(acts[3]), _P(g), B, H, W, 32, C4, kh, kw, 1, N.ACT_NONE, slope,
                    ops._dt(gy), st())
+        g = inject(g, 3)
         # ---- wide layers 4, 3, 2 (indices 3, 2, 1)
         for li in (3, 2, 1):
             Cout, Cin = ws[li].shape[0], ws[li].shape[1]
@@ -217,7 +257,7 @@ class _DiscStack(Function):
             gprev = torch.empty(B, H, W, Cin, device=dev, dtype=dt)
             N.call("mv_dconv_cl_fwd", _P(g), _P(_packs.get(params[2 * li], dt, 1)), None, _P(acts[li - 1]), _P(gprev), B, H, W, Cout, Cin,
                    kh, kw, 1, N.ACT_NONE, slope, ops._dt(g), st())
-            g = gprev
+            g = inject(gprev, li - 1)
         # ---- first layer
         C1 = ws[0].shape[0]
         if need_w:
@@ -238,7 +278,46 @@ class _DiscStack(Function):
             gx0 = torch.empty_like(x0)
             ws = torch.empty(N.lib().mv_dfirst_dgrad_workspace_bytes(B, H, W) // 4, device=dev, dtype=torch.float32)
             N.call("mv_dfirst_dgrad_cl", _P(g), _P(_cache.get(params[0], dt)), _P(gx0), _P(ws), B, H, W, C1, kh, kw, ops._dt(g), st())
+        return (gx0, *grads)
+
+
+class _DiscStack(Function):
+    @staticmethod
+    def forward(ctx, x0, slope, *params):
+        return _Stack.forward(ctx, x0, slope, params)[0]
+
+    @staticmethod
+    def backward(ctx, gy):
+        gx0, *grads = _Stack.backward(ctx, gy)
         return (gx0, None, *grads)
+
+
+class _DiscStackFM(Function):
+    """(x0, slope, real_feats, *params) -> (out, fm): the stack's output and fm = sum_l mean|a_l - real_l| over its four hidden
+    feature maps, real_feats = the real waveform's maps from disc_features (constants: D(real).detach())."""
+
+    @staticmethod
+    def forward(ctx, x0, slope, real_feats, *params):
+        ctx.set_materialize_grads(False)
+        out, _, fm = _Stack.forward(ctx, x0, slope, params, _cl_buffers(real_feats))
+        return out, fm
+
+    @staticmethod
+    def backward(ctx, gy, gfm):
+        gx0, *grads = _Stack.backward(ctx, gy, gfm, first_param=3)
+        return (gx0, None, None, *grads)
+
+
+class _Discard:
+    """Context of a forward whose saved tensors nobody will ask for."""
+
+    def save_for_backward(self, *ts):
+        pass
+
+
+def _features(x0, slope, *params):
+    out, acts, _ = _Stack.forward(_Discard(), x0, slope, params)
+    return out, [_logical(a, x0.dim()) for a in acts]
 
 
 _cache = ops._ParamCache()
@@ -251,12 +330,34 @@ def supported(x, blk) -> bool:
     return x.dtype == torch.float32 and x.is_cuda and getattr(blk, "fp32_operands", "exact") == "split"
 
 
-def disc_stack(x0, blk, slope=0.1):
-    convs = [blk.conv_layers[i] for i in (0, 2, 4, 6, 8)]
+def _params(blk):
     params = []
-    for c in convs:
+    for c in (blk.conv_layers[i] for i in (0, 2, 4, 6, 8)):
         params += [c.weight, c.bias]
+    return params
+
+
+def disc_stack(x0, blk, slope=0.1):
     from . import functional as Fn
     if Fn.DISPATCH == "torch_ops":
-        return Fn._t().OPS.disc_conv_stack(x0, float(slope), *params)
-    return _DiscStack.apply(x0, slope, *params)
+        return Fn._t().OPS.disc_conv_stack(x0, float(slope), *_params(blk))
+    return _DiscStack.apply(x0, slope, *_params(blk))
+
+
+def disc_features(x0, blk, slope=0.1):
+    """The stack under no_grad: (out, [a_1..a_4]), a_l = hidden conv l after its LeakyReLU with logical shape [B,C,H,W] / [B,C,W], a
+    permuted view of the stack's channels-last buffer."""
+    from . import functional as Fn
+    with torch.no_grad():
+        if Fn.DISPATCH == "torch_ops":
+            out, feats = Fn._t().OPS.disc_conv_stack_features(x0, float(slope), *_params(blk))
+            return out, list(feats)
+        return _features(x0, slope, *_params(blk))
+
+
+def disc_stack_fm(x0, blk, real_feats, slope=0.1):
+    """(out, fm) of _DiscStackFM."""
+    from . import functional as Fn
+    if Fn.DISPATCH == "torch_ops":
+        return Fn._t().OPS.disc_conv_stack_fm(x0, float(slope), *real_feats, *_params(blk))
+    return _DiscStackFM.apply(x0, slope, list(real_feats), *_params(blk))

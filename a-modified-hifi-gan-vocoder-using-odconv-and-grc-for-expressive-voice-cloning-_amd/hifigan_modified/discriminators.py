@@ -10,6 +10,7 @@ split into hi + lo bf16 and three products per MAC (disc_fused.py, ~2^-16 relati
 """
 from __future__ import annotations
 
+import weakref
 from typing import List
 
 import torch
@@ -39,7 +40,50 @@ class _Fp32Operands:
         return self
 
 
-class Discriminator2D(_Fp32Operands, nn.Module):
+class DiscFeatures(list):
+    """The four hidden feature maps `features()` returned, with the module, input shape and dtype they belong to."""
+
+    def __init__(self, feats, owner, shape, dtype):
+        super().__init__(feats)
+        self.owner, self.shape, self.dtype = weakref.ref(owner), tuple(shape), dtype
+
+
+class _FeatureMatching:
+    """`features(x)` / `forward_fm(x, real_feats)` of one sub-discriminator (HiFi-GAN's feature-matching term over the hidden maps,
+    defined by this build: DESIGN.md section 5b); `_fn` is functional.disc2d / disc1d."""
+
+    def features(self, x: torch.Tensor):
+        """Under no_grad: (out, feats) with feats = [a_1..a_4], a_l = hidden conv l after its LeakyReLU(0.1), logical shape
+        [B,C,H,W] (2D) / [B,C,W] (1D), channels 32, 64, 128, 256."""
+        out, feats = self._fn(x, self, "features")
+        return out, DiscFeatures(feats, self, x.shape, x.dtype)
+
+    def forward_fm(self, x: torch.Tensor, real_feats):
+        """(out, fm): forward(x) and fm = sum_l mean|a_l(x) - real_l| (fp32, 0-dim) with real_feats = features(real)[1] of THIS
+        module at the same input shape and dtype, taken as constants."""
+        if not isinstance(real_feats, DiscFeatures) or real_feats.owner() is not self:
+            raise ValueError("forward_fm: real_feats must be what features() of this very module returned")
+        if real_feats.shape != tuple(x.shape) or real_feats.dtype != x.dtype:
+            raise ValueError(f"forward_fm: real_feats were taken at {real_feats.shape} {real_feats.dtype}, x is {tuple(x.shape)} {x.dtype}")
+        return self._fn(x, self, "fm", real_feats)
+
+
+class _FeatureMatchingList:
+    """List-valued `features` / `forward_fm` over `self.discriminators`."""
+
+    def features(self, x: torch.Tensor):
+        return [d.features(x) for d in self.discriminators]
+
+    def forward_fm(self, x: torch.Tensor, real_feats):
+        """real_feats: one features()[1] per sub-discriminator (or the (out, feats) pairs features() returned)."""
+        if len(real_feats) != len(self.discriminators):
+            raise ValueError(f"forward_fm: {len(self.discriminators)} feature lists expected, got {len(real_feats)}")
+        return [d.forward_fm(x, r[1] if isinstance(r, tuple) else r) for d, r in zip(self.discriminators, real_feats)]
+
+
+class Discriminator2D(_FeatureMatching, _Fp32Operands, nn.Module):
+    _fn = staticmethod(Fn.disc2d)
+
     def __init__(self, period: int):
         super().__init__()
         self.period = period
@@ -54,7 +98,9 @@ class Discriminator2D(_Fp32Operands, nn.Module):
         return Fn.disc2d(x, self)
 
 
-class Discriminator1D(_Fp32Operands, nn.Module):
+class Discriminator1D(_FeatureMatching, _Fp32Operands, nn.Module):
+    _fn = staticmethod(Fn.disc1d)
+
     def __init__(self, scale: int):
         super().__init__()
         self.scale = scale
@@ -70,7 +116,7 @@ class Discriminator1D(_Fp32Operands, nn.Module):
         return Fn.disc1d(x, self)
 
 
-class MultiPeriodDiscriminator(_Fp32Operands, nn.Module):
+class MultiPeriodDiscriminator(_FeatureMatchingList, _Fp32Operands, nn.Module):
     def __init__(self, periods: List[int] = [2, 3, 5, 7, 11]):
         super().__init__()
         self.periods = periods
@@ -80,7 +126,7 @@ class MultiPeriodDiscriminator(_Fp32Operands, nn.Module):
         return [d(x) for d in self.discriminators]
 
 
-class MultiScaleDiscriminator(_Fp32Operands, nn.Module):
+class MultiScaleDiscriminator(_FeatureMatchingList, _Fp32Operands, nn.Module):
     def __init__(self, scales: List[int] = [1, 2, 4]):
         super().__init__()
         self.scales = scales

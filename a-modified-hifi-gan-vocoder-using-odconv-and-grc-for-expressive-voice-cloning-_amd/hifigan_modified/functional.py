@@ -8,6 +8,8 @@ parameter gradients are produced in fp32 and cast to the parameter's dtype.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 from torch.autograd import Function
 
@@ -777,32 +779,49 @@ def _convs(seq):
     return [seq[i] for i in (0, 2, 4, 6, 8)]
 
 
-def disc2d(x, blk):
-    """discriminators.py:68-84."""
+def _disc_chain(h, x, blk, conv, form, real):
+    """One sub-discriminator's five layers on the folded / pooled input h, in one of three forms:
+      "out"       the output (discriminators.py:56-66 / :97-107)
+      "features"  under no_grad: (out, [a_1..a_4]), a_l = hidden conv l after its LeakyReLU(0.1), logical [B,C,H,W] / [B,C,W]
+      "fm"        (out, fm) with fm = sum_l mean|a_l - real_l| (fp32, 0-dim), real = another waveform's "features" list, a constant
+    16-bit storage and split fp32 run the channels-last MFMA stack (csrc/disc_fused.hip), which forms fm and its gradient with
+    mv_fm_l1 / mv_fm_inject on its own buffers; the generic fp32 chain forms the same quantity from its per-layer tensors with l1."""
+    from . import disc_fused
+    if disc_fused.supported(x, blk):
+        if form == "out":
+            return disc_fused.disc_stack(h, blk)
+        return disc_fused.disc_features(h, blk) if form == "features" else disc_fused.disc_stack_fm(h, blk, real)
+    feats, fm = [], None
+    with torch.no_grad() if form == "features" else contextlib.nullcontext():
+        for li, c in enumerate(_convs(blk.conv_layers)):
+            h = conv(h, c, "lrelu" if li < 4 else None)
+            if li < 4 and form == "features":
+                feats.append(h)
+            elif li < 4 and form == "fm":
+                if real[li].shape != h.shape or real[li].dtype != h.dtype:
+                    raise ValueError(f"feature matching: real feature {tuple(real[li].shape)} {real[li].dtype} does not match the "
+                                     f"stack's {tuple(h.shape)} {h.dtype}")
+                t = l1(h, real[li].detach())
+                fm = t if fm is None else fm + t
+    return h if form == "out" else ((h, feats) if form == "features" else (h, fm))
+
+
+def disc2d(x, blk, form="out", real=None):
+    """discriminators.py:68-84; `form`: see _disc_chain."""
     B, C, T = x.shape
     if T % blk.period == 0:
         h = x.contiguous().view(B, C, blk.period, T // blk.period)   # exact multiple: the fold is a pure view
     else:
         h = _t().OPS.mpd_fold(x, blk.period) if DISPATCH == "torch_ops" else _MpdFold.apply(x, blk.period)
-    from . import disc_fused
-    if disc_fused.supported(x, blk):      # 16-bit storage or split fp32: channels-last MFMA stack (csrc/disc_fused.hip)
-        return disc_fused.disc_stack(h, blk)
-    for li, conv in enumerate(_convs(blk.conv_layers)):
-        h = conv2d(h, conv.weight, conv.bias, (1, 1), "lrelu" if li < 4 else None, 0.1)
-    return h
+    return _disc_chain(h, x, blk, lambda h, c, act: conv2d(h, c.weight, c.bias, (1, 1), act, 0.1), form, real)
 
 
-def disc1d(x, blk):
-    """discriminators.py:109-117."""
+def disc1d(x, blk, form="out", real=None):
+    """discriminators.py:109-117; `form`: see _disc_chain."""
     h = x
     if blk.scale > 1:
         h = _t().OPS.avg_pool1d(x, blk.scale) if DISPATCH == "torch_ops" else _AvgPool.apply(x, blk.scale)
-    from . import disc_fused
-    if disc_fused.supported(x, blk):
-        return disc_fused.disc_stack(h, blk)
-    for li, conv in enumerate(_convs(blk.conv_layers)):
-        h = conv1d(h, conv.weight, conv.bias, padding=7, act="lrelu" if li < 4 else None, slope=0.1)
-    return h
+    return _disc_chain(h, x, blk, lambda h, c, act: conv1d(h, c.weight, c.bias, padding=7, act=act, slope=0.1), form, real)
 
 
 # ----------------------------------------------------------------------------------------------- losses

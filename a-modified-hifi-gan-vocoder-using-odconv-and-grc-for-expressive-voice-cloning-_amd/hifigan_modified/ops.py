@@ -608,6 +608,40 @@ def scale_(x, factor=1.0, factor_dev=None):
     return x
 
 
+def _same_layout(name, a, *others):
+    """The feature-matching kernels walk memory linearly: every tensor must be dense and share one shape, dtype and stride order."""
+    for t in others:
+        if t.shape != a.shape or t.dtype != a.dtype or t.stride() != a.stride():
+            raise ValueError(f"{name}: tensors must share shape, dtype and strides, got {tuple(a.shape)} {a.dtype} {a.stride()} and "
+                             f"{tuple(t.shape)} {t.dtype} {t.stride()}")
+    order = sorted(range(a.dim()), key=lambda d: (-a.stride(d), d))
+    if a.numel() == 0 or not a.permute(order).is_contiguous():
+        raise ValueError(f"{name}: tensors must be non-empty and dense (a permuted view of a contiguous buffer is)")
+
+
+def fm_l1(a, b, acc=None, scale=None):
+    """acc (fp32 [1], a new zeroed one when None) += scale * sum|a - b|; scale None: 1 / numel, the mean (mv_fm_l1).  a and b in any
+    one dense layout, e.g. the permuted views of the discriminator stacks' channels-last buffers."""
+    _need_gpu(a, b)
+    _same_layout("fm_l1", a, b)
+    if acc is None:
+        acc = _scalars.take(a.device)
+    N.call("mv_fm_l1", _p(a), _p(b), a.numel(), float(1.0 / a.numel() if scale is None else scale), _p(acc), _dt(a), _stream())
+    return acc
+
+
+def fm_inject(g, af, ar, upstream, slope=0.1, coef=None):
+    """In place g += coef * upstream[0] * sign(af - ar) * LeakyReLU'(af) (mv_fm_inject); coef None: 1 / numel.  upstream: one fp32
+    element on the device."""
+    _need_gpu(g, af, ar, upstream)
+    _same_layout("fm_inject", g, af, ar)
+    if upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("fm_inject: upstream must be a one-element fp32 tensor")
+    N.call("mv_fm_inject", _p(g), _p(af), _p(ar), g.numel(), _p(upstream), float(1.0 / g.numel() if coef is None else coef),
+           float(slope), _dt(g), _stream())
+    return g
+
+
 def mel_loss(wave, fb, target=None, n_fft=1024, hop=256, clampv=1e-5, weight=1.0, backward=False, want_mel=False,
              kind=0):
     # the C entry point receives no tensor sizes for target / fb: a wrong shape would be an out-of-bounds device read or a

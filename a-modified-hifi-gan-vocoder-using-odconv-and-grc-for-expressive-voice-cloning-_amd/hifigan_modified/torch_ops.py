@@ -17,6 +17,7 @@ Operators (schemas as registered; ``act``: 0 none, 1 LeakyReLU, 2 tanh, 3 SiLU; 
   conv1d, conv2d, group_norm, film                   grc_lora.py:32-68,108-129,157-163; discriminators.py:56-66,97-107
   grc_mrf_block, generator_forward                   fused inference: grc_lora.py:157-163, SURVEY.md appendix A
   avg_pool1d, mpd_fold, disc_conv_stack              discriminators.py:72-79,94,56-66,97-107
+  disc_conv_stack_fm, disc_conv_stack_features       the stack with HiFi-GAN's hidden-map feature matching
   gan_loss, mel_loss, mel_spectrogram                complete_vocoder.py:89-184, conditioned_hifigan.py:262-265; DESIGN.md section 2
   fused_adamw_, fused_adamw_dev_, fused_adamw_hp_, fused_adamw_clip_   conditioned_hifigan.py:219 (torch.optim.AdamW semantics): one
                                                      kernel, the per-step inputs by value or from device memory, clipped or not
@@ -77,7 +78,7 @@ class _Ctx:
         self.saved_tensors = ts
 
     def set_materialize_grads(self, v):
-        pass
+        self.materialize_grads = v           # handed to the operator's autograd context (setup below)
 
 
 def _refuse_cpu(name):
@@ -114,6 +115,8 @@ def _register(name, schema, cls, pack, fmap):
             raise RuntimeError(f"{NS}::{name}: forward record does not belong to this call")
         ctx.mv_attrs = {k: v for k, v in rec.__dict__.items() if k not in ("saved_tensors", "needs_input_grad")}
         ctx.mv_nsaved = len(rec.saved_tensors)
+        if rec.__dict__.get("materialize_grads") is False:
+            ctx.set_materialize_grads(False)      # an unused output's gradient arrives as None, not as zeros
         ctx.save_for_backward(*rec.saved_tensors)
 
     def backward(ctx, *grads):
@@ -206,6 +209,11 @@ def _install():
     names = ", ".join(f"Tensor w{i}, Tensor b{i}" for i in range(1, 6))
     _register("disc_conv_stack", f"(Tensor x, float slope, {names}) -> Tensor", disc_fused._DiscStack,
               lambda x, slope, *params: (x, slope, *params), list(range(12)))
+    # feature matching over the hidden maps (defined by this build): r1..r4 = the real waveform's features
+    reals = ", ".join(f"Tensor r{i}" for i in range(1, 5))
+    _register("disc_conv_stack_fm", f"(Tensor x, float slope, {reals}, {names}) -> (Tensor, Tensor)", disc_fused._DiscStackFM,
+              lambda x, slope, r1, r2, r3, r4, *params: (x, slope, [r1, r2, r3, r4], *params), [0, 1, None] + list(range(6, 16)))
+    _forward_only("disc_conv_stack_features", f"(Tensor x, float slope, {names}) -> (Tensor, Tensor[])", disc_fused._features)
 
     # ---- losses
     _register("gan_loss", "(Tensor x, Tensor? y, int kind, float c, float weight) -> Tensor", Fn._Loss,
@@ -342,6 +350,16 @@ def _install_fakes():
     def _stack(x, slope, *params):
         return x.new_empty((x.shape[0], 1) + tuple(x.shape[2:]))
     torch.library.register_fake(f"{NS}::disc_conv_stack", _stack, lib=_LIB)
+
+    def _stack_fm(x, slope, r1, r2, r3, r4, *params):
+        return _stack(x, slope, *params), x.new_empty((), dtype=torch.float32)
+    torch.library.register_fake(f"{NS}::disc_conv_stack_fm", _stack_fm, lib=_LIB)
+
+    def _stack_features(x, slope, *params):
+        B, sp = x.shape[0], tuple(x.shape[2:])
+        feats = [x.new_empty((B,) + sp + (w.shape[0],)) for w in params[0:8:2]]           # channels-last buffers, logical views of them
+        return _stack(x, slope, *params), [f.permute(0, 3, 1, 2) if x.dim() == 4 else f.permute(0, 2, 1) for f in feats]
+    torch.library.register_fake(f"{NS}::disc_conv_stack_features", _stack_features, lib=_LIB)
 
     @fake("gan_loss")
     def _(x, y, kind, c, weight):

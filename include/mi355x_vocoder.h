@@ -339,6 +339,18 @@ int mv_scale(void* x, const float* factor_dev, float factor, long n, int dtype, 
 /* y = x * factor * (factor_dev ? factor_dev[0] : 1), out of place (loss backward: the saved gradient times the upstream scalar). */
 int mv_scale_to(const void* x, void* y, const float* factor_dev, float factor, long n, int dtype, void* stream);
 
+/* Feature matching over the discriminators' HIDDEN feature maps.   defined by this build: it generalises the
+ * output-only L1 of complete_vocoder.py:118,127 to every intermediate map of every sub-discriminator (Kong et al. 2020).  a, b, g,
+ * af, ar: n elements of `dtype` in any one layout (the stacks pass their channels-last buffers).
+ *   mv_fm_l1:     acc[0] += scale * sum |a[i] - b[i]| (fp32, one atomic per workgroup; acc zeroed by the caller with a fill kernel).
+ *   mv_fm_inject: g[i] += coef * upstream_dev[0] * sign(af[i] - ar[i]) * (af[i] >= 0 ? 1 : slope), in place, fp32 arithmetic, one
+ *                 rounding.  g is the gradient with respect to the PRE-activation of af (what mv_dconv_cl_fwd's act_save mode
+ *                 leaves), the last factor LeakyReLU' with that mode's convention at 0; sign(0) = 0.  upstream_dev: one fp32 on the
+ *                 device (the loss term's incoming gradient: a captured step never reads it on the host); g must not alias af / ar. */
+int mv_fm_l1(const void* a, const void* b, long n, float scale, float* acc, int dtype, void* stream);
+int mv_fm_inject(void* g, const void* af, const void* ar, long n, const float* upstream_dev, float coef, float slope, int dtype,
+                 void* stream);
+
 /* Log-mel spectrogram (+ L1 loss against `target`, fp32 [B][n_mels][T/hop]) of wave [B][1][T]; defined by this build (the
  * reference has only placeholders: complete_vocoder.py:210-212, conditioned_hifigan.py:269-274).  Frames: reflect pad
  * (n_fft-hop)/2, periodic Hann, |rFFT| (in-LDS radix-2 FFT when n_fft is a power of two, direct DFT otherwise), mel = fb [n_mels][n_fft/2+1] (fp32) @ mag, log(max(., clamp)).

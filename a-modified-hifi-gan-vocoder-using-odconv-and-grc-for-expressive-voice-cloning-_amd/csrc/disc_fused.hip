@@ -1644,7 +1644,7 @@ extern "C" size_t mv_dconv_wgrad_workspace_bytes(int Cin, int Cout, int kh, int 
 
 template <typename T, int TW_>
 static int dwgrad_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, int dil, hipStream_t s,
-                         int xW = 0, long sample_stride = 0) {
+                         int xW = 0, long sample_stride = 0, bool dry = false) {   // dry: every check, no launch
   constexpr int WT = 128;
   const int wsplit = cdiv(W, WT);
   const int halo = (TW_ - 1) * dil;
@@ -1664,6 +1664,7 @@ static int dwgrad_launch(const void* x, const void* g, float* gws, float* gb, in
   if (sample_stride > 0) cpw = H * wsplit;            // one workgroup per (tile, sample)
   groups = (int)((nchunks + cpw - 1) / cpw);
   if (groups > 65535) return MV_ERR_UNSUPPORTED;
+  if (dry) return MV_OK;
   dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), groups);
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const T*)x, (const T*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw, dil,
                      xW > 0 ? xW : W, sample_stride);
@@ -1671,7 +1672,8 @@ static int dwgrad_launch(const void* x, const void* g, float* gws, float* gb, in
 }
 
 template <typename T, int MO>
-static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, hipStream_t s) {
+static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, hipStream_t s,
+                          bool dry = false) {
   constexpr int WT = 64, OT = 32 * MO;
   const int wsplit = cdiv(W, WT);
   const size_t lds = 2 * (size_t)WT * (OT * 2 + 32) + 9 * (size_t)(WT + 2) * 160;
@@ -1686,6 +1688,7 @@ static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, i
   const int cpw = (int)((nchunks + groups - 1) / groups);
   groups = (int)((nchunks + cpw - 1) / cpw);
   if (groups > 65535) return MV_ERR_UNSUPPORTED;
+  if (dry) return MV_OK;
   dim3 grid(cdiv(Cin, 64), cdiv(Cout, OT), groups);
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const T*)x, (const T*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw);
   return MV_OK;
@@ -1725,18 +1728,18 @@ static int dwgrad_f32_dispatch(const void* x, const void* g, float* ws, float* g
 
 template <typename T>
 static int dwgrad_dispatch(const void* x, const void* g, float* ws, float* gb, int B, int H, int W, int Cin, int Cout, int kh, int kw,
-                           int dil, hipStream_t s) {
+                           int dil, hipStream_t s, bool dry = false) {
   if (kh == 3 && kw == 3 && dil == 1)
-    return Cout >= 128 ? dwgrad3_launch<T, 4>(x, g, ws, gb, B, H, W, Cin, Cout, s) : dwgrad3_launch<T, 2>(x, g, ws, gb, B, H, W, Cin, Cout, s);
+    return Cout >= 128 ? dwgrad3_launch<T, 4>(x, g, ws, gb, B, H, W, Cin, Cout, s, dry) : dwgrad3_launch<T, 2>(x, g, ws, gb, B, H, W, Cin, Cout, s, dry);
   if (kh == 3 && kw == 3) return MV_ERR_UNSUPPORTED;
   if (kh != 1) return MV_ERR_UNSUPPORTED;
   switch (kw) {
-    case 1: return dwgrad_launch<T, 1>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 3: return dwgrad_launch<T, 3>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 5: return dwgrad_launch<T, 5>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 7: return dwgrad_launch<T, 7>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 11: return dwgrad_launch<T, 11>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
-    case 15: return dwgrad_launch<T, 15>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s);
+    case 1: return dwgrad_launch<T, 1>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
+    case 3: return dwgrad_launch<T, 3>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
+    case 5: return dwgrad_launch<T, 5>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
+    case 7: return dwgrad_launch<T, 7>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
+    case 11: return dwgrad_launch<T, 11>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
+    case 15: return dwgrad_launch<T, 15>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
     default: return MV_ERR_UNSUPPORTED;
   }
 }
@@ -1746,6 +1749,12 @@ extern "C" int mv_dconv_wgrad_cl(const void* x, const void* g, float* gw, float*
   MV_CHECK_ARG(x && g && gw && workspace && B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0 && dil_w >= 1);
   MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0);
   if (dtype == MV_F32 && !dwgrad_f32_ok(kh, kw, dil_w)) return MV_ERR_UNSUPPORTED;   // fp32: the discriminator geometries only
+  // 16-bit: ask the dispatcher (dry run: every check, no launch) before the fills below touch the workspace and gb
+  if (dtype == MV_BF16 || dtype == MV_F16) {
+    const int ok = dtype == MV_BF16 ? dwgrad_dispatch<bf16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, nullptr, true)
+                                    : dwgrad_dispatch<f16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, nullptr, true);
+    if (ok != MV_OK) return ok;
+  }
   hipStream_t s = (hipStream_t)stream;
   const size_t wn = (size_t)Cout * Cin * kh * kw;
   if (gb && gb == workspace + wn) {                  // bias sums placed right behind the workspace: one fill instead of two
@@ -1812,7 +1821,9 @@ __global__ __launch_bounds__(256) void tap_matrix_kernel(const T* __restrict__ s
     alignas(16) T o8[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) st<T>(o8 + j, v[j]);
-    *reinterpret_cast<u32x4*>(out + pos * 16 + half * 8) = *reinterpret_cast<u32x4*>(o8);
+#pragma unroll
+    for (int q = 0; q < (int)sizeof(T) / 2; ++q)      // 8 taps: one 16-byte store for 16-bit storage, two for fp32
+      reinterpret_cast<u32x4*>(out + pos * 16 + half * 8)[q] = reinterpret_cast<u32x4*>(o8)[q];
   }
 }
 

@@ -1355,6 +1355,16 @@ __global__ __launch_bounds__(256) void put_channel_kernel(const T* __restrict__ 
 
 using namespace mv;
 
+// dtype dispatch of the kernels that exist for 16-bit storage only: BODY sees `T`
+#define MV_DISPATCH16(dtype, ...)                                       \
+  switch (dtype) {                                                      \
+    case MV_BF16: { using T = mv::bf16; __VA_ARGS__; break; }           \
+    case MV_F16: { using T = mv::f16; __VA_ARGS__; break; }             \
+    default: return MV_ERR_UNSUPPORTED; }
+
+// workgroups of a grid-stride kernel: one per `per` elements, at most `cap`
+static inline unsigned grid_cap(long n, int per, unsigned cap) { const long g = (n + per - 1) / per; return g > cap ? cap : (unsigned)g; }
+
 extern "C" size_t mv_dconv_packed_bytes(int Cout, int Cin, int kh, int kw, int dtype) {
   return (size_t)Cout * Cin * kh * kw * (dtype == MV_F32 ? 4 : 2);
 }
@@ -1365,7 +1375,7 @@ extern "C" int mv_dconv_pack_pad(const void* w, int param_dtype, void* packed, i
   const int Mr = flip ? Cinp : Coutp, Kc = flip ? Coutp : Cinp;
   MV_CHECK_ARG(Mr % 16 == 0 && Kc % 32 == 0);
   const long total = (long)Coutp * Cinp * kh * kw;
-  const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+  const unsigned grid = grid_cap(total, 256, 4096);
   MV_DISPATCH(dtype, {
     switch (param_dtype) {
       case MV_F32: hipLaunchKernelGGL((dconv_pack_kernel<T, float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)w, (T*)packed, Cout, Cin, kh, kw, flip, Coutp, Cinp); break;
@@ -1391,147 +1401,157 @@ extern "C" int mv_dconv_multi_pack(const void* descs_dev, int n, void* stream) {
   return MV_OK;
 }
 
-template <typename T, int NWV, int MW, int NB>
-static int dconv_launch(const void* x, const void* wp, const void* bias, const void* actsave, void* y, DcP p, hipStream_t s) {
-  using M = Mma<T>;
-  const int prow = NB * 16 + (p.kw - 1) * p.dil;
-  const size_t xb = (size_t)p.kh * prow * lds_row_stride(p.Cin * M::ES, M::ES);
-  const size_t ob = (size_t)NB * 16 * (NWV * MW * 16 * M::ES + 16);
-  const size_t lds = xb > ob ? xb : ob;
-  if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
-  const int cpr = p.Cin * M::ES / 16;
-  if (cpr > NWV * 64) return MV_ERR_UNSUPPORTED;   // staging: a thread keeps its 16-byte piece of every row it copies
-  auto kern = dconv_cl_kernel<T, NWV, MW, NB>;
-  static size_t lds_set = 0;
-  if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
-  dim3 grid(cdiv(p.W, NB * 16), cdiv(p.Cout / 16, NWV * MW), p.B * p.H);
-  if (grid.z > 65535) return MV_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, s, (const T*)x, (const T*)wp, (const T*)bias, (const T*)actsave, (T*)y, p);
-  return MV_OK;
-}
+// ------------------------------------------------------------------------------------------------ forward dispatch: plan, then launch
+// The whole decision for a shape, made without touching the GPU: which instantiation, its tile and its launch geometry.
+struct DconvFwdPlan {
+  bool wide;                    // false: dconv_cl_kernel<T,NWV,MW,NB> (whole Cin in LDS), true: dconv_cl_wide_kernel<T,PS,MW,NB,CCH,NWV> (chunked)
+  int ps, mw, nb, cch, nwv;     // the template parameters (ps = cch = 0 in the whole-Cin family)
+  int npos, cchunk, rows;       // positions along W, input channels staged at a time and output rows of one workgroup
+  size_t lds;
+  int gx, gy, gz, threads;
+};
 
-static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias, const void* act_save, void* y,
-                             int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int act, float slope, int dtype,
-                             void* stream, const void* head_pf, float* head_z, int head_taps) {
-  MV_CHECK_ARG(x && packed && y && B > 0 && H > 0 && W > 0 && Cin % 32 == 0 && Cout % 16 == 0 && (kh & 1) && (kw & 1));
+static int dconv_fwd_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int dtype, bool has_head, bool has_act_save,
+                          DconvFwdPlan* pl) {
+  MV_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin % 32 == 0 && Cout % 16 == 0 && (kh & 1) && (kw & 1));
   MV_CHECK_ARG(dil_w >= 1 && (kw - 1) * dil_w <= 128);
-  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)packed & 15) == 0 && Cout % 8 == 0);
-  if (head_pf && (Cout != 256 || dtype == MV_F32 || act_save || B * H > 65535)) return MV_ERR_UNSUPPORTED;   // needs the 256-row workgroups
-  DcP p{B, H, W, Cin, Cout, kh, kw, act, slope, kh * kw * (Cin / 32), Cin / 32, dil_w, Cin, head_pf, head_z, head_taps};
-  int rc = MV_ERR_DTYPE;
+  const long bh = (long)B * H;
+  if (has_head && (Cout != 256 || dtype == MV_F32 || has_act_save || bh > 65535)) return MV_ERR_UNSUPPORTED;   // needs the 256-row workgroups
+  if (dtype != MV_F32 && dtype != MV_BF16 && dtype != MV_F16) return MV_ERR_DTYPE;
+  const int es = dtype == MV_F32 ? 4 : 2, halo = (kw - 1) * dil_w;
+  // a tile of either family (ps = cch = 0: whole Cin, one position slice): PS position slices x NWV/PS row groups of waves; the x rows
+  // are staged as 16-bit planes (fp32: a hi and a lo plane, twice the 16-bit tile), the output tile in the storage type
+  auto tile = [&](int ps, int mw, int nb, int cch, int nwv) {
+    const int slices = ps ? ps : 1;
+    DconvFwdPlan w{ps != 0, ps, mw, nb, cch, nwv, slices * nb * 16, cch ? cch : Cin, nwv / slices * mw * 16};
+    const size_t xb = (size_t)(es / 2) * kh * (w.npos + halo) * lds_row_stride(w.cchunk * 2, 2);
+    const size_t ob = (size_t)w.npos * (w.rows * es + 16);
+    w.lds = xb > ob ? xb : ob;
+    w.gx = cdiv(W, w.npos); w.gy = cdiv(Cout, w.rows); w.gz = (int)bh; w.threads = nwv * 64;
+    return w;
+  };
+  // whole-Cin family, 4 waves, 16-bit storage; staging: a thread keeps its 16-byte piece of every row it copies (Cin / 8 <= 256 threads)
+  auto whole = [&](int mw, int nb) {
+    *pl = tile(0, mw, nb, 0, 4);
+    return pl->lds > 160 * 1024 || Cin * 2 / 16 > pl->threads || bh > 65535 ? MV_ERR_UNSUPPORTED : MV_OK;
+  };
   if (dtype == MV_F32) {
     // split-operand fp32 (Mma<float>, three bf16 products per MAC): 4 waves = 2 position slices x 2 row groups, 128 positions and
     // 32 / 64 / 128 rows per workgroup.  The hi/lo planes cost 4 bytes per staged channel and position, twice the 16-bit tile, so
     // the channel chunk is 32 for 3x3 (75 KB) and 64 for the one-row kernels (45 KB): two workgroups per CU either way
-    if (B * H > 65535) return MV_ERR_UNSUPPORTED;
+    if (bh > 65535) return MV_ERR_UNSUPPORTED;
     const int cch = (kh == 1 && Cin % 64 == 0) ? 64 : 32;
     const int rows = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
-    p.cchunk = cch;
-    const size_t xb = 2 * (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(cch * 2, 2);
-    const size_t ob = (size_t)128 * (rows * 4 + 16);
-    const size_t ldsb = xb > ob ? xb : ob;
-    if (ldsb > 160 * 1024) return MV_ERR_UNSUPPORTED;
-    dim3 grid(cdiv(W, 128), cdiv(Cout, rows), B * H);
-    hipStream_t st_ = (hipStream_t)stream;
-#define MV_F32W(MW_, CC_) do { auto kern = dconv_cl_wide_kernel<float, 2, MW_, 4, CC_, 4>; static size_t lds_set_f = 0; \
-      if (ldsb > lds_set_f) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); lds_set_f = ldsb; } \
-      hipLaunchKernelGGL(kern, grid, dim3(256), ldsb, st_, (const float*)x, (const float*)packed, (const float*)bias, (const float*)act_save, (float*)y, p); } while (0)
-#define MV_F32R(CC_) do { if (rows == 128) MV_F32W(4, CC_); else if (rows == 64) MV_F32W(2, CC_); else MV_F32W(1, CC_); } while (0)
-    if (cch == 64) MV_F32R(64); else MV_F32R(32);
-#undef MV_F32R
-#undef MV_F32W
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    *pl = tile(2, rows / 32, 4, cch, 4);
+    return pl->lds > 160 * 1024 ? MV_ERR_UNSUPPORTED : MV_OK;
   }
-  if (B * H <= 65535) {
+  if (bh <= 65535) {
     // 8-wave chunked variant: picked where it measured faster than the whole-Cin tile (tools/bench_dconv.py, B=32):
     // every wide input (Cin > 128), and narrow outputs of 3x3 layers, where the whole-Cin kernel leaves waves idle
-    const size_t full = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(Cin * 2, 2);
+    const size_t full = (size_t)kh * (128 + halo) * lds_row_stride(Cin * 2, 2);
     const bool big3x3 = kh == 3 && Cin == 128 && Cout >= 256;      // 256 rows per workgroup: 4 M-tiles per B fragment
     bool use = full > 160 * 1024 || Cin > 128 || (kh == 3 && Cin >= 64 && Cout <= 128) || (kh == 1 && Cin == 64 && Cout == 32) || big3x3;
-    if (head_pf && !(big3x3 || (kh == 3 && Cin % 64 == 0 && Cin >= 128 && W >= 256))) use = false;   // the chunked tiles below have 256 rows only there
+    if (has_head && !(big3x3 || (kh == 3 && Cin % 64 == 0 && Cin >= 128 && W >= 256))) use = false;   // the chunked tiles below have 256 rows only there
     // 3x3 layers with >= 128 channels on both sides: 256-position tiles (8 column blocks per wave: one weight fragment feeds
     // 8 MFMAs) with 64-channel chunks measured 6-13 % faster than 128-position tiles; the k15 layers measured slower
     const bool nb8 = kh == 3 && Cin % 64 == 0 && Cin >= 128 && Cout >= 128 && W >= 256;
     // 4-wave form of the 256-row tile: 256 rows x 128 positions, 64-channel chunks, TWO workgroups per CU - one's
     // staging and epilogue run under the other's MFMAs; every wave keeps the 64 x 128 tile of the 8-wave kernel
-    if (kh == 3 && Cin % 64 == 0 && Cout % 256 == 0 && W >= 128) {
-      p.cchunk = 64;
-      const size_t xb = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(64 * 2, 2);
-      const size_t ob = (size_t)128 * (256 * 2 + 16);
-      const size_t ldsb = xb > ob ? xb : ob;
-      dim3 grid(cdiv(W, 128), Cout / 256, B * H);
-#define MV_W4(TT) do { auto kern = dconv_cl_wide_kernel<TT, 1, 4, 8, 64, 4>; static size_t lds_set_4 = 0; \
-        if (ldsb > lds_set_4) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); lds_set_4 = ldsb; } \
-        hipLaunchKernelGGL(kern, grid, dim3(256), ldsb, (hipStream_t)stream, (const TT*)x, (const TT*)packed, (const TT*)bias, (const TT*)act_save, (TT*)y, p); } while (0)
-      if (dtype == MV_BF16) MV_W4(bf16); else MV_W4(f16);
-#undef MV_W4
-      MV_LAUNCH_CHECK();
-      return MV_OK;
-    }
+    if (kh == 3 && Cin % 64 == 0 && Cout % 256 == 0 && W >= 128) { *pl = tile(1, 4, 8, 64, 4); return MV_OK; }
     // 128-row outputs of the big 3x3 layers (the data gradient of 128->256): 2 waves per workgroup, each with the 64 x 128 tile;
     // 32-channel chunks keep the tile at 37 KB, so FOUR workgroups share a CU (445 -> 425 us; 64 input channels measured slower)
-    if (kh == 3 && Cin % 32 == 0 && Cin >= 128 && Cout == 128 && W >= 128) {
-      p.cchunk = 32;
-      const size_t xb = (size_t)kh * (128 + (kw - 1) * dil_w) * lds_row_stride(32 * 2, 2);
-      const size_t ob = (size_t)128 * (128 * 2 + 16);
-      const size_t ldsb = xb > ob ? xb : ob;
-      dim3 grid(cdiv(W, 128), 1, B * H);
-#define MV_W2(TT) do { auto kern = dconv_cl_wide_kernel<TT, 1, 4, 8, 32, 2>; static size_t lds_set_2 = 0; \
-        if (ldsb > lds_set_2) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); lds_set_2 = ldsb; } \
-        hipLaunchKernelGGL(kern, grid, dim3(128), ldsb, (hipStream_t)stream, (const TT*)x, (const TT*)packed, (const TT*)bias, (const TT*)act_save, (TT*)y, p); } while (0)
-      if (dtype == MV_BF16) MV_W2(bf16); else MV_W2(f16);
-#undef MV_W2
-      MV_LAUNCH_CHECK();
-      return MV_OK;
-    }
+    if (kh == 3 && Cin % 32 == 0 && Cin >= 128 && Cout == 128 && W >= 128) { *pl = tile(1, 4, 8, 32, 2); return MV_OK; }
     const int npos = nb8 ? 256 : 128;
-    p.cchunk = nb8 ? 64 : (Cin > 128 ? 128 : Cin);
-    if (use && Cin % p.cchunk == 0 && (p.cchunk == 128 || p.cchunk == 64 || p.cchunk == 32)) {
-      const size_t xb = (size_t)kh * (npos + (kw - 1) * dil_w) * lds_row_stride(p.cchunk * 2, 2);
+    const int cchunk = nb8 ? 64 : (Cin > 128 ? 128 : Cin);
+    if (use && Cin % cchunk == 0 && (cchunk == 128 || cchunk == 64 || cchunk == 32)) {
       int rows = (big3x3 || (nb8 && Cout >= 256)) ? 256 : Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
       // short sequences (the conditioning producers: a few hundred positions in all): narrower row tiles until the grid covers the chip
       if (!nb8 && !big3x3)
-        while (rows > 32 && (long)cdiv(W, npos) * cdiv(Cout, rows) * B * H < 256) rows >>= 1;
-      const size_t ob = (size_t)npos * (rows * 2 + 16);
-      const size_t ldsb = xb > ob ? xb : ob;
-      if (ldsb <= 160 * 1024) {
-        hipStream_t st_ = (hipStream_t)stream;
-        dim3 grid(cdiv(W, npos), cdiv(Cout, rows), B * H);
-#define MV_WIDE(TT, PS_, MW_, NB_, CC_) do { \
-          auto kern = dconv_cl_wide_kernel<TT, PS_, MW_, NB_, CC_>; \
-          static size_t lds_set_w = 0; \
-          if (ldsb > lds_set_w) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); lds_set_w = ldsb; } \
-          hipLaunchKernelGGL(kern, grid, dim3(512), ldsb, st_, (const TT*)x, (const TT*)packed, (const TT*)bias, (const TT*)act_save, (TT*)y, p); } while (0)
-#define MV_WIDE_R(TT, CC_) do { if (rows == 256) MV_WIDE(TT, 2, 4, 4, CC_); else if (rows == 128) MV_WIDE(TT, 2, 2, 4, CC_); else if (rows == 64) MV_WIDE(TT, 4, 2, 2, CC_); else MV_WIDE(TT, 4, 1, 2, CC_); } while (0)
-#define MV_WIDE_T(TT) do { if (nb8) { if (rows == 256) MV_WIDE(TT, 2, 4, 8, 64); else MV_WIDE(TT, 2, 2, 8, 64); } \
-          else if (p.cchunk == 128) MV_WIDE_R(TT, 128); else if (p.cchunk == 64) MV_WIDE_R(TT, 64); else MV_WIDE_R(TT, 32); } while (0)
-        if (dtype == MV_BF16) MV_WIDE_T(bf16); else MV_WIDE_T(f16);
-#undef MV_WIDE_T
-#undef MV_WIDE_R
-#undef MV_WIDE
-        MV_LAUNCH_CHECK();
-        return MV_OK;
-      }
+        while (rows > 32 && cdiv(W, npos) * cdiv(Cout, rows) * bh < 256) rows >>= 1;
+      const int nb = nb8 ? 8 : 4;
+      const DconvFwdPlan w = rows == 256 ? tile(2, 4, nb, cchunk, 8) : rows == 128 ? tile(2, 2, nb, cchunk, 8)
+                           : rows == 64 ? tile(4, 2, 2, cchunk, 8) : tile(4, 1, 2, cchunk, 8);
+      if (w.lds <= 160 * 1024) { *pl = w; return MV_OK; }
     }
-    p.cchunk = Cin;
   }
-  auto whole = [&](auto tag) {   // 16-bit storage only: fp32 returned above
-    using T = decltype(tag);
-    hipStream_t s_ = (hipStream_t)stream;
-    if (Cout >= 256) {        // 4 waves x 64 rows: one B fragment feeds 4 MFMAs (LDS reads per MFMA halved), two workgroups per CU
-      rc = dconv_launch<T, 4, 4, 8>(x, packed, bias, act_save, y, p, s_);
-    } else if (Cout >= 128) {
-      rc = dconv_launch<T, 4, 2, 8>(x, packed, bias, act_save, y, p, s_);
-      if (rc == MV_ERR_UNSUPPORTED) rc = dconv_launch<T, 4, 2, 4>(x, packed, bias, act_save, y, p, s_);
-    } else {
-      rc = dconv_launch<T, 4, 1, 8>(x, packed, bias, act_save, y, p, s_);
-      if (rc == MV_ERR_UNSUPPORTED) rc = dconv_launch<T, 4, 1, 4>(x, packed, bias, act_save, y, p, s_);
-    }
+  // whole-Cin tile, 16-bit storage only (fp32 returned above)
+  if (Cout >= 256) return whole(4, 8);      // 4 waves x 64 rows: one B fragment feeds 4 MFMAs (LDS reads per MFMA halved), two workgroups per CU
+  const int mw = Cout >= 128 ? 2 : 1;
+  const int rc = whole(mw, 8);
+  return rc == MV_ERR_UNSUPPORTED ? whole(mw, 4) : rc;
+}
+
+// set-attribute-then-launch of a kernel with dynamic LDS: one high-water mark of the attribute per instantiation
+template <auto KERN, typename... A>
+static void lds_launch(dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
+  static size_t lds_set = 0;
+  if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
+  hipLaunchKernelGGL(KERN, grid, dim3(threads), lds, s, args...);
+}
+
+struct DconvFwdArgs { const void *x, *wp, *bias, *actsave; void* y; DcP p; hipStream_t s; };
+using DconvFwdLaunch = void (*)(const DconvFwdPlan&, const DconvFwdArgs&);
+
+template <typename T, auto KERN>      // both families take the same arguments
+static void dconv_fwd_launch(const DconvFwdPlan& pl, const DconvFwdArgs& a) {
+  lds_launch<KERN>(dim3(pl.gx, pl.gy, pl.gz), pl.threads, pl.lds, a.s, (const T*)a.x, (const T*)a.wp, (const T*)a.bias, (const T*)a.actsave,
+                   (T*)a.y, a.p);
+}
+
+// every instantiation a plan can name, its template parameters beside its launcher: the library holds these forward kernels and no others
+struct DconvFwdArm { int ps, mw, nb, cch, nwv; DconvFwdLaunch launch; };
+template <typename T, int PS, int MW, int NB, int CCH, int NWV>
+constexpr DconvFwdArm wide_arm{PS, MW, NB, CCH, NWV, dconv_fwd_launch<T, dconv_cl_wide_kernel<T, PS, MW, NB, CCH, NWV>>};
+template <typename T, int MW, int NB>
+constexpr DconvFwdArm whole_arm{0, MW, NB, 0, 4, dconv_fwd_launch<T, dconv_cl_kernel<T, 4, MW, NB>>};
+template <typename T>
+constexpr DconvFwdArm dconv_fwd_arms16[] = {
+    wide_arm<T, 1, 4, 8, 64, 4>,  wide_arm<T, 1, 4, 8, 32, 2>,  wide_arm<T, 2, 4, 8, 64, 8>,  wide_arm<T, 2, 2, 8, 64, 8>,   // two direct, two nb8
+    wide_arm<T, 2, 4, 4, 128, 8>, wide_arm<T, 2, 2, 4, 128, 8>, wide_arm<T, 4, 2, 2, 128, 8>, wide_arm<T, 4, 1, 2, 128, 8>,
+    wide_arm<T, 2, 2, 4, 64, 8>,  wide_arm<T, 4, 2, 2, 64, 8>,  wide_arm<T, 4, 1, 2, 64, 8>,
+    whole_arm<T, 4, 8>, whole_arm<T, 2, 8>, whole_arm<T, 2, 4>, whole_arm<T, 1, 8>, whole_arm<T, 1, 4>,
+};
+constexpr DconvFwdArm dconv_fwd_arms32[] = {
+    wide_arm<float, 2, 4, 4, 64, 4>, wide_arm<float, 2, 2, 4, 64, 4>, wide_arm<float, 2, 1, 4, 64, 4>,
+    wide_arm<float, 2, 4, 4, 32, 4>, wide_arm<float, 2, 2, 4, 32, 4>, wide_arm<float, 2, 1, 4, 32, 4>,
+};
+
+// the launcher of a plan's instantiation; a plan that names one the tables do not hold is a bug in dconv_fwd_plan: nullptr
+static DconvFwdLaunch dconv_fwd_launcher(const DconvFwdPlan& pl, int dtype) {
+  const auto find = [&](const auto& arms) -> DconvFwdLaunch {
+    for (const DconvFwdArm& a : arms)
+      if (a.ps == pl.ps && a.mw == pl.mw && a.nb == pl.nb && a.cch == pl.cch && a.nwv == pl.nwv) return a.launch;
+    return nullptr;
   };
-  if (dtype == MV_BF16) whole(bf16{}); else if (dtype == MV_F16) whole(f16{}); else return MV_ERR_DTYPE;
+  return dtype == MV_F32 ? find(dconv_fwd_arms32) : dtype == MV_BF16 ? find(dconv_fwd_arms16<bf16>) : find(dconv_fwd_arms16<f16>);
+}
+
+static int dconv_cl_fwd_impl(const void* x, const void* packed, const void* bias, const void* act_save, void* y,
+                             int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int act, float slope, int dtype,
+                             void* stream, const void* head_pf, float* head_z, int head_taps) {
+  MV_CHECK_ARG(x && packed && y);
+  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)packed & 15) == 0);
+  DconvFwdPlan pl;
+  const int rc = dconv_fwd_plan(B, H, W, Cin, Cout, kh, kw, dil_w, dtype, head_pf != nullptr, act_save != nullptr, &pl);
   if (rc != MV_OK) return rc;
+  const DconvFwdLaunch launch = dconv_fwd_launcher(pl, dtype);
+  if (!launch) return MV_ERR_UNSUPPORTED;
+  const DcP p{B, H, W, Cin, Cout, kh, kw, act, slope, kh * kw * (Cin / 32), Cin / 32, dil_w, pl.cchunk, head_pf, head_z, head_taps};
+  launch(pl, DconvFwdArgs{x, packed, bias, act_save, y, p, (hipStream_t)stream});
   MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+// out: PS, MW, NB, CCH, NWV, npos, cchunk, rows, LDS bytes, grid x, y, z (see the header)
+extern "C" int mv_dconv_cl_fwd_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int dtype, int with_head,
+                                    int with_act_save, int* out) {
+  MV_CHECK_ARG(out);
+  DconvFwdPlan pl;
+  const int rc = dconv_fwd_plan(B, H, W, Cin, Cout, kh, kw, with_head ? 1 : dil_w, dtype, with_head != 0, with_act_save != 0, &pl);
+  if (rc != MV_OK) return rc;
+  if (!dconv_fwd_launcher(pl, dtype)) return MV_ERR_UNSUPPORTED;
+  const int v[12] = {pl.ps, pl.mw, pl.nb, pl.cch, pl.nwv, pl.npos, pl.cchunk, pl.rows, (int)pl.lds, pl.gx, pl.gy, pl.gz};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
   return MV_OK;
 }
 
@@ -1554,8 +1574,8 @@ extern "C" size_t mv_dhead_workspace_bytes(int B, int H, int W) { return sizeof(
 
 extern "C" int mv_dhead_pack(const void* w, int param_dtype, void* packed, int C, int kh, int kw, int dtype, void* stream) {
   MV_CHECK_ARG(w && packed && C == DH_C && kh * kw <= 16);
-  if (dtype == MV_F32) return MV_ERR_UNSUPPORTED;
-  MV_DISPATCH(dtype, {
+  if (dtype != MV_BF16 && dtype != MV_F16) return dtype == MV_F32 ? MV_ERR_UNSUPPORTED : MV_ERR_DTYPE;   // 16-bit storage only
+  MV_DISPATCH16(dtype, {
     T* pf = (T*)packed; T* pd = pf + (C / 32) * 512;
     switch (param_dtype) {
       case MV_F32: hipLaunchKernelGGL((dhead_pack_kernel<T, float>), dim3(24), dim3(256), 0, (hipStream_t)stream, (const float*)w, pf, pd, C, kh * kw); break;
@@ -1572,30 +1592,23 @@ template <typename T>
 static void dhead_fwd_launch(const void* x, const void* packed, const void* bias, float* ws, void* y, int B, int H, int W, int kh,
                              int kw, hipStream_t s) {
   const long npos = (long)B * H * W;
-  const long groups = (npos + 15) / 16;
-  const int grid = (int)((groups + 3) / 4 > 4096 ? 4096 : (groups + 3) / 4);
-  hipLaunchKernelGGL((dhead_z_kernel<T, DH_C>), dim3(grid), dim3(256), 0, s, (const T*)x, (const T*)packed, ws, npos, kh * kw);
-  hipLaunchKernelGGL(dhead_sum_kernel<T>, dim3((unsigned)((npos + 255) / 256 > 4096 ? 4096 : (npos + 255) / 256)), dim3(256), 0, s,
-                     ws, (const T*)bias, (T*)y, B, H, W, kh, kw, 0);
+  hipLaunchKernelGGL((dhead_z_kernel<T, DH_C>), dim3(grid_cap((npos + 15) / 16, 4, 4096)), dim3(256), 0, s, (const T*)x, (const T*)packed, ws,
+                     npos, kh * kw);
+  hipLaunchKernelGGL(dhead_sum_kernel<T>, dim3(grid_cap(npos, 256, 4096)), dim3(256), 0, s, ws, (const T*)bias, (T*)y, B, H, W, kh, kw, 0);
 }
 
 extern "C" int mv_dhead_fwd(const void* x, const void* packed, const void* bias, float* workspace, void* y, int B, int H, int W,
                             int C, int kh, int kw, int dtype, void* stream) {
   MV_CHECK_ARG(x && packed && workspace && y && B > 0 && H > 0 && W > 0 && C == DH_C && kh * kw <= 16 && ((uintptr_t)x & 15) == 0);
-  if (dtype == MV_BF16) dhead_fwd_launch<bf16>(x, packed, bias, workspace, y, B, H, W, kh, kw, (hipStream_t)stream);
-  else if (dtype == MV_F16) dhead_fwd_launch<f16>(x, packed, bias, workspace, y, B, H, W, kh, kw, (hipStream_t)stream);
-  else return MV_ERR_UNSUPPORTED;
+  MV_DISPATCH16(dtype, dhead_fwd_launch<T>(x, packed, bias, workspace, y, B, H, W, kh, kw, (hipStream_t)stream));
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
 
 extern "C" int mv_dhead_sum(const float* workspace, const void* bias, void* y, int B, int H, int W, int kh, int kw, int dtype, void* stream) {
   MV_CHECK_ARG(workspace && y && B > 0 && H > 0 && W > 0 && kh * kw <= 16);
-  const long npos = (long)B * H * W;
-  const unsigned grid = (unsigned)((npos + 255) / 256 > 4096 ? 4096 : (npos + 255) / 256);
-  if (dtype == MV_BF16) hipLaunchKernelGGL(dhead_sum_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, workspace, (const bf16*)bias, (bf16*)y, B, H, W, kh, kw, 0);
-  else if (dtype == MV_F16) hipLaunchKernelGGL(dhead_sum_kernel<f16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, workspace, (const f16*)bias, (f16*)y, B, H, W, kh, kw, 0);
-  else return MV_ERR_UNSUPPORTED;
+  MV_DISPATCH16(dtype, hipLaunchKernelGGL(dhead_sum_kernel<T>, dim3(grid_cap((long)B * H * W, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                                          workspace, (const T*)bias, (T*)y, B, H, W, kh, kw, 0));
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
@@ -1604,15 +1617,9 @@ extern "C" int mv_dhead_dgrad(const void* g, const void* packed, const void* xsa
                               int kw, float slope, int dtype, void* stream) {
   MV_CHECK_ARG(g && packed && xsave && gx && B > 0 && H > 0 && W > 0 && C == DH_C && kh * kw <= 16);
   MV_CHECK_ARG(((uintptr_t)xsave & 15) == 0 && ((uintptr_t)gx & 15) == 0);
-  const long groups = ((long)B * H * W + 15) / 16;
-  const int grid = (int)((groups + 3) / 4 > 4096 ? 4096 : (groups + 3) / 4);
-  if (dtype == MV_BF16)
-    hipLaunchKernelGGL(dhead_dgrad_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)g,
-                       (const bf16*)packed + (C / 32) * 512, (const bf16*)xsave, (bf16*)gx, B, H, W, kh, kw, slope);
-  else if (dtype == MV_F16)
-    hipLaunchKernelGGL(dhead_dgrad_kernel<f16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f16*)g,
-                       (const f16*)packed + (C / 32) * 512, (const f16*)xsave, (f16*)gx, B, H, W, kh, kw, slope);
-  else return MV_ERR_UNSUPPORTED;
+  const unsigned grid = grid_cap(((long)B * H * W + 15) / 16, 4, 4096);
+  MV_DISPATCH16(dtype, hipLaunchKernelGGL(dhead_dgrad_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)g,
+                                          (const T*)packed + (C / 32) * 512, (const T*)xsave, (T*)gx, B, H, W, kh, kw, slope));
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
@@ -1623,10 +1630,9 @@ extern "C" int mv_dhead_wgrad(const void* g, const void* x, float* gw, float* gb
   MV_HIP(mvi_zero_async(gw, sizeof(float) * (size_t)kh * kw * C, (hipStream_t)stream));
   MV_HIP(mvi_zero_async(gb, sizeof(float), (hipStream_t)stream));
   MV_CHECK_ARG(kw <= DH_MAXTAPS && H <= 65535);
-  if (dtype != MV_F32 && ((uintptr_t)x & 15) == 0) {   // 16-byte channel vectors: register-tiled reduction
+  if ((dtype == MV_BF16 || dtype == MV_F16) && ((uintptr_t)x & 15) == 0) {   // 16-byte channel vectors: register-tiled reduction
     int rc = MV_ERR_UNSUPPORTED;
-    if (dtype == MV_BF16) rc = dtap_launch<bf16>(x, g, gw, gb, B, H, W, C, kh, kw, 1, 1, C, 2, (hipStream_t)stream);
-    else if (dtype == MV_F16) rc = dtap_launch<f16>(x, g, gw, gb, B, H, W, C, kh, kw, 1, 1, C, 2, (hipStream_t)stream);
+    MV_DISPATCH16(dtype, rc = dtap_launch<T>(x, g, gw, gb, B, H, W, C, kh, kw, 1, 1, C, 2, (hipStream_t)stream));
     if (rc == MV_OK) { MV_LAUNCH_CHECK(); return MV_OK; }
   }
   const int chunk = 256;
@@ -1642,157 +1648,153 @@ extern "C" size_t mv_dconv_wgrad_workspace_bytes(int Cin, int Cout, int kh, int 
   return sizeof(float) * (size_t)Cin * Cout * kh * kw;
 }
 
-template <typename T, int TW_>
-static int dwgrad_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, int dil, hipStream_t s,
-                         int xW = 0, long sample_stride = 0, bool dry = false) {   // dry: every check, no launch
-  constexpr int WT = 128;
-  const int wsplit = cdiv(W, WT);
-  const int halo = (TW_ - 1) * dil;
-  if (halo > 64) return MV_ERR_UNSUPPORTED;
-  const size_t lds = 2 * (size_t)(WT + (WT + halo)) * 160;
-  if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
-  auto kern = dconv_wgrad_kernel<T, 1, TW_, WT>;
-  static size_t lds_set = 0;
-  if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
-  const long nchunks = (long)B * H * wsplit;
-  if (nchunks > (1L << 30)) return MV_ERR_UNSUPPORTED;
-  const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
-  // one workgroup per CU is resident (LDS); one round of workgroups keeps the final fp32 atomics to a few tens of MB
+// ------------------------------------------------------------------------------------------------ weight-gradient dispatch: plan, then launch
+struct DconvWgradPlan {
+  bool three;                   // false: dconv_wgrad_kernel<T,TH,TW,WT>, true: dconv_wgrad3_kernel<T,MO> with MO = otile / 32
+  int th, tw;                   // taps of the instantiation (kh x kw; 1 x 2 for the per-sample form of mv_odconvT_wgrad_mfma)
+  int wt, otile;                // positions of a chunk, output channels of a tile
+  int wsplit, nchunks, cpw, groups;   // chunks per image row, in all and per workgroup; workgroups along the positions
+  size_t lds;
+  int gx, gy, gz;
+  int xW;                       // row pitch of x in positions, and the per-sample output stride (0: all samples summed)
+  long sample_stride;
+};
+
+// chunks per workgroup: one workgroup per CU is resident (LDS); one round of workgroups keeps the final fp32 atomics to a few tens of MB
+static int wgrad_split(long nchunks, int tiles) {
   constexpr int target = 256;
   int groups = target / tiles; if (groups < 1) groups = 1; if (groups > nchunks) groups = (int)nchunks;
-  int cpw = (int)((nchunks + groups - 1) / groups);
-  if (sample_stride > 0) cpw = H * wsplit;            // one workgroup per (tile, sample)
-  groups = (int)((nchunks + cpw - 1) / cpw);
-  if (groups > 65535) return MV_ERR_UNSUPPORTED;
-  if (dry) return MV_OK;
-  dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), groups);
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const T*)x, (const T*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw, dil,
-                     xW > 0 ? xW : W, sample_stride);
+  return (int)((nchunks + groups - 1) / groups);
+}
+
+// xW, sample_stride: 0 except for mv_odconvT_wgrad_mfma, whose rows are one position longer than W and whose samples keep their own tile
+static int dconv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil, int dtype, int xW, long sample_stride,
+                            DconvWgradPlan* pl) {
+  MV_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0 && dil >= 1);
+  DconvWgradPlan w{};
+  w.th = kh; w.tw = kw; w.otile = 64; w.xW = xW > 0 ? xW : W; w.sample_stride = sample_stride;
+  long rows_staged = 0;         // 3x3: x rows a walk over every chunk stages
+  if (dtype == MV_F32) {
+    // fp32 split operands, the discriminator geometries only: the staged chunk is twice the 16-bit one (hi + lo planes), so it holds 64
+    // positions of a k15 row or 32 of a 3x3 row (91 / 86 KB for both buffers)
+    if (!(dil == 1 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 15)))) return MV_ERR_UNSUPPORTED;
+    w.wt = kh == 1 ? 64 : 32;
+    w.lds = 2 * 2 * (size_t)(w.wt + kh * (w.wt + kw - 1)) * 160;
+  } else if (dtype != MV_BF16 && dtype != MV_F16) {
+    return MV_ERR_UNSUPPORTED;
+  } else if (kh == 3 && kw == 3) {
+    if (dil != 1) return MV_ERR_UNSUPPORTED;
+    w.three = true; w.wt = 64; w.otile = Cout >= 128 ? 128 : 64;
+    w.lds = 2 * (size_t)w.wt * (w.otile * 2 + 32) + 9 * (size_t)(w.wt + 2) * 160;
+    rows_staged = (long)B * cdiv(W, w.wt) * (H + 2);
+  } else {
+    if (kh != 1) return MV_ERR_UNSUPPORTED;
+    if (sample_stride > 0 ? kw != 2 : !(kw == 1 || kw == 3 || kw == 5 || kw == 7 || kw == 11 || kw == 15)) return MV_ERR_UNSUPPORTED;
+    const int halo = (kw - 1) * dil;
+    if (halo > 64) return MV_ERR_UNSUPPORTED;
+    w.wt = 128;
+    w.lds = 2 * (size_t)(w.wt + (w.wt + halo)) * 160;
+  }
+  if (w.lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
+  w.wsplit = cdiv(W, w.wt);
+  const long nchunks = (long)B * H * w.wsplit;            // 3x3: chunk = (sample, strip, row), rows fastest
+  if (nchunks > (1L << 30) || rows_staged > (1L << 30)) return MV_ERR_UNSUPPORTED;
+  w.gx = cdiv(Cin, 64); w.gy = cdiv(Cout, w.otile); w.nchunks = (int)nchunks;
+  w.cpw = sample_stride > 0 ? H * w.wsplit : wgrad_split(nchunks, w.gx * w.gy);   // per-sample form: one workgroup per (tile, sample)
+  w.groups = w.gz = (int)((nchunks + w.cpw - 1) / w.cpw);
+  if (w.groups > 65535) return MV_ERR_UNSUPPORTED;
+  *pl = w;
   return MV_OK;
+}
+
+struct DwgradArgs { const void *x, *g; float *gws, *gb; int B, H, W, Cin, Cout, dil; hipStream_t s; };
+
+template <typename T, int TH, int TW, int WT>
+static void dwgrad_launch(const DconvWgradPlan& pl, const DwgradArgs& a) {
+  lds_launch<dconv_wgrad_kernel<T, TH, TW, WT>>(dim3(pl.gx, pl.gy, pl.gz), 512, pl.lds, a.s, (const T*)a.x, (const T*)a.g, a.gws, a.gb, a.B, a.H, a.W,
+                                                a.Cin, a.Cout, pl.wsplit, pl.nchunks, pl.cpw, a.dil, pl.xW, pl.sample_stride);
 }
 
 template <typename T, int MO>
-static int dwgrad3_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, hipStream_t s,
-                          bool dry = false) {
-  constexpr int WT = 64, OT = 32 * MO;
-  const int wsplit = cdiv(W, WT);
-  const size_t lds = 2 * (size_t)WT * (OT * 2 + 32) + 9 * (size_t)(WT + 2) * 160;
-  auto kern = dconv_wgrad3_kernel<T, MO>;
-  static bool lds_set = false;
-  if (!lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = true; }
-  const long nchunks = (long)B * wsplit * H;               // chunk = (sample, strip, row), rows fastest
-  if (nchunks > (1L << 30) || (long)B * wsplit * (H + 2) > (1L << 30)) return MV_ERR_UNSUPPORTED;
-  const int tiles = cdiv(Cin, 64) * cdiv(Cout, OT);
-  constexpr int target = 256;
-  int groups = target / tiles; if (groups < 1) groups = 1; if (groups > nchunks) groups = (int)nchunks;
-  const int cpw = (int)((nchunks + groups - 1) / groups);
-  groups = (int)((nchunks + cpw - 1) / cpw);
-  if (groups > 65535) return MV_ERR_UNSUPPORTED;
-  if (dry) return MV_OK;
-  dim3 grid(cdiv(Cin, 64), cdiv(Cout, OT), groups);
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const T*)x, (const T*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw);
-  return MV_OK;
+static void dwgrad3_launch(const DconvWgradPlan& pl, const DwgradArgs& a) {
+  lds_launch<dconv_wgrad3_kernel<T, MO>>(dim3(pl.gx, pl.gy, pl.gz), 512, pl.lds, a.s, (const T*)a.x, (const T*)a.g, a.gws, a.gb, a.B, a.H, a.W, a.Cin,
+                                         a.Cout, pl.wsplit, pl.nchunks, pl.cpw);
 }
 
-// fp32 split operands: the staged chunk is twice the 16-bit one (hi + lo planes), so it holds 64 positions of a k15 row or 32 of
-// a 3x3 row (91 / 86 KB for both buffers)
-template <int TH, int TW>
-static int dwgrad_f32_launch(const void* x, const void* g, float* gws, float* gb, int B, int H, int W, int Cin, int Cout, hipStream_t s) {
-  constexpr int WT = TH == 1 ? 64 : 32;
-  const int wsplit = cdiv(W, WT);
-  const size_t lds = 2 * 2 * (size_t)(WT + TH * (WT + TW - 1)) * 160;
-  auto kern = dconv_wgrad_kernel<float, TH, TW, WT>;
-  static bool lds_set = false;
-  if (!lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = true; }
-  const long nchunks = (long)B * H * wsplit;
-  if (nchunks > (1L << 30)) return MV_ERR_UNSUPPORTED;
-  const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
-  constexpr int target = 256;
-  int groups = target / tiles; if (groups < 1) groups = 1; if (groups > nchunks) groups = (int)nchunks;
-  const int cpw = (int)((nchunks + groups - 1) / groups);
-  groups = (int)((nchunks + cpw - 1) / cpw);
-  if (groups > 65535) return MV_ERR_UNSUPPORTED;
-  dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), groups);
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const float*)x, (const float*)g, gws, gb, B, H, W, Cin, Cout, wsplit, (int)nchunks, cpw, 1,
-                     W, 0L);
-  return MV_OK;
-}
-
-static bool dwgrad_f32_ok(int kh, int kw, int dil) { return dil == 1 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 15)); }
-
-static int dwgrad_f32_dispatch(const void* x, const void* g, float* ws, float* gb, int B, int H, int W, int Cin, int Cout, int kh, int kw,
-                               hipStream_t s) {
-  if (kh == 3) return dwgrad_f32_launch<3, 3>(x, g, ws, gb, B, H, W, Cin, Cout, s);
-  return dwgrad_f32_launch<1, 15>(x, g, ws, gb, B, H, W, Cin, Cout, s);
-}
-
+// the plan's instantiation: fp32 3x3 and 1x15; 16-bit 3x3 with 64 / 128 output channels per tile, and 1xk
 template <typename T>
-static int dwgrad_dispatch(const void* x, const void* g, float* ws, float* gb, int B, int H, int W, int Cin, int Cout, int kh, int kw,
-                           int dil, hipStream_t s, bool dry = false) {
-  if (kh == 3 && kw == 3 && dil == 1)
-    return Cout >= 128 ? dwgrad3_launch<T, 4>(x, g, ws, gb, B, H, W, Cin, Cout, s, dry) : dwgrad3_launch<T, 2>(x, g, ws, gb, B, H, W, Cin, Cout, s, dry);
-  if (kh == 3 && kw == 3) return MV_ERR_UNSUPPORTED;
-  if (kh != 1) return MV_ERR_UNSUPPORTED;
-  switch (kw) {
-    case 1: return dwgrad_launch<T, 1>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
-    case 3: return dwgrad_launch<T, 3>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
-    case 5: return dwgrad_launch<T, 5>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
-    case 7: return dwgrad_launch<T, 7>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
-    case 11: return dwgrad_launch<T, 11>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
-    case 15: return dwgrad_launch<T, 15>(x, g, ws, gb, B, H, W, Cin, Cout, dil, s, 0, 0, dry);
-    default: return MV_ERR_UNSUPPORTED;
+static int dwgrad_run(const DconvWgradPlan& pl, const DwgradArgs& a) {
+  if constexpr (sizeof(T) == 4) {
+    if (pl.th == 3) dwgrad_launch<float, 3, 3, 32>(pl, a); else dwgrad_launch<float, 1, 15, 64>(pl, a);
+  } else if (pl.three) {
+    if (pl.otile == 128) dwgrad3_launch<T, 4>(pl, a); else dwgrad3_launch<T, 2>(pl, a);
+  } else {
+    switch (pl.tw) {
+      case 1: dwgrad_launch<T, 1, 1, 128>(pl, a); break;
+      case 2: dwgrad_launch<T, 1, 2, 128>(pl, a); break;
+      case 3: dwgrad_launch<T, 1, 3, 128>(pl, a); break;
+      case 5: dwgrad_launch<T, 1, 5, 128>(pl, a); break;
+      case 7: dwgrad_launch<T, 1, 7, 128>(pl, a); break;
+      case 11: dwgrad_launch<T, 1, 11, 128>(pl, a); break;
+      case 15: dwgrad_launch<T, 1, 15, 128>(pl, a); break;
+      default: return MV_ERR_UNSUPPORTED;       // a plan without a kernel: a bug in dconv_wgrad_plan
+    }
   }
+  return MV_OK;
+}
+
+// mv_dconv_wgrad_cl (zero-fill the workspace and gb, reorder) and mv_dconv_wgrad_cl_pz (caller-zeroed workspace with the bias sums
+// behind it, finalize); nothing is written before the plan has accepted the shape
+static int dconv_wgrad_cl_impl(const void* x, const void* g, float* gw, float* gb, float* workspace, int B, int H, int W, int Cin, int Cout,
+                               int kh, int kw, int dil_w, int dtype, void* stream, bool caller_zeroed) {
+  MV_CHECK_ARG(x && g && gw && workspace);
+  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0);
+  DconvWgradPlan pl;
+  const int ok = dconv_wgrad_plan(B, H, W, Cin, Cout, kh, kw, dil_w, dtype, 0, 0, &pl);
+  if (ok != MV_OK) return ok;
+  hipStream_t s = (hipStream_t)stream;
+  const long total = (long)Cout * Cin * kh * kw;
+  if (!caller_zeroed) {
+    if (gb && gb == workspace + total) {             // bias sums placed right behind the workspace: one fill instead of two
+      MV_HIP(mvi_zero_async(workspace, sizeof(float) * (size_t)(total + Cout), s));
+    } else {
+      MV_HIP(mvi_zero_async(workspace, sizeof(float) * (size_t)total, s));
+      if (gb) MV_HIP(mvi_zero_async(gb, sizeof(float) * (size_t)Cout, s));
+    }
+  }
+  const DwgradArgs a{x, g, workspace, caller_zeroed ? workspace + total : gb, B, H, W, Cin, Cout, dil_w, s};
+  int rc = MV_OK;
+  MV_DISPATCH(dtype, rc = dwgrad_run<T>(pl, a));
+  if (rc != MV_OK) return rc;
+  if (caller_zeroed)
+    hipLaunchKernelGGL(dconv_wgrad_finalize_kernel, dim3(grid_cap(total + Cout, 256, 2048)), dim3(256), 0, s, workspace, gw, gb, Cout * Cin,
+                       kh * kw, Cout);
+  else
+    hipLaunchKernelGGL(dconv_wgrad_reorder_kernel, dim3(grid_cap(total, 256, 2048)), dim3(256), 0, s, workspace, gw, Cout * Cin, kh * kw);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
 }
 
 extern "C" int mv_dconv_wgrad_cl(const void* x, const void* g, float* gw, float* gb, float* workspace, int B, int H, int W, int Cin,
                                  int Cout, int kh, int kw, int dil_w, int dtype, void* stream) {
-  MV_CHECK_ARG(x && g && gw && workspace && B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0 && dil_w >= 1);
-  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0);
-  if (dtype == MV_F32 && !dwgrad_f32_ok(kh, kw, dil_w)) return MV_ERR_UNSUPPORTED;   // fp32: the discriminator geometries only
-  // 16-bit: ask the dispatcher (dry run: every check, no launch) before the fills below touch the workspace and gb
-  if (dtype == MV_BF16 || dtype == MV_F16) {
-    const int ok = dtype == MV_BF16 ? dwgrad_dispatch<bf16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, nullptr, true)
-                                    : dwgrad_dispatch<f16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, nullptr, true);
-    if (ok != MV_OK) return ok;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const size_t wn = (size_t)Cout * Cin * kh * kw;
-  if (gb && gb == workspace + wn) {                  // bias sums placed right behind the workspace: one fill instead of two
-    MV_HIP(mvi_zero_async(workspace, sizeof(float) * (wn + Cout), s));
-  } else {
-    MV_HIP(mvi_zero_async(workspace, sizeof(float) * wn, s));
-    if (gb) MV_HIP(mvi_zero_async(gb, sizeof(float) * (size_t)Cout, s));
-  }
-  int rc = MV_ERR_UNSUPPORTED;
-  if (dtype == MV_BF16) rc = dwgrad_dispatch<bf16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, s);
-  else if (dtype == MV_F16) rc = dwgrad_dispatch<f16>(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, dil_w, s);
-  else if (dtype == MV_F32) rc = dwgrad_f32_dispatch(x, g, workspace, gb, B, H, W, Cin, Cout, kh, kw, s);
-  if (rc != MV_OK) return rc;
-  const long total = (long)Cout * Cin * kh * kw;
-  hipLaunchKernelGGL(dconv_wgrad_reorder_kernel, dim3((unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256)), dim3(256),
-                     0, s, workspace, gw, Cout * Cin, kh * kw);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  return dconv_wgrad_cl_impl(x, g, gw, gb, workspace, B, H, W, Cin, Cout, kh, kw, dil_w, dtype, stream, false);
 }
 
 extern "C" int mv_dconv_wgrad_cl_pz(const void* x, const void* g, float* gw, float* gb, float* workspace, int B, int H, int W, int Cin,
                                     int Cout, int kh, int kw, int dil_w, int dtype, void* stream) {
-  MV_CHECK_ARG(x && g && gw && workspace && B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0 && dil_w >= 1);
-  MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0);
-  if (dtype == MV_F32 && !dwgrad_f32_ok(kh, kw, dil_w)) return MV_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const long total = (long)Cout * Cin * kh * kw;
-  int rc = MV_ERR_UNSUPPORTED;
-  if (dtype == MV_BF16) rc = dwgrad_dispatch<bf16>(x, g, workspace, workspace + total, B, H, W, Cin, Cout, kh, kw, dil_w, s);
-  else if (dtype == MV_F16) rc = dwgrad_dispatch<f16>(x, g, workspace, workspace + total, B, H, W, Cin, Cout, kh, kw, dil_w, s);
-  else if (dtype == MV_F32) rc = dwgrad_f32_dispatch(x, g, workspace, workspace + total, B, H, W, Cin, Cout, kh, kw, s);
-  if (rc != MV_OK) return rc;
-  hipLaunchKernelGGL(dconv_wgrad_finalize_kernel, dim3((unsigned)((total + Cout + 255) / 256 > 2048 ? 2048 : (total + Cout + 255) / 256)),
-                     dim3(256), 0, s, workspace, gw, gb, Cout * Cin, kh * kw, Cout);
-  MV_LAUNCH_CHECK();
-  return MV_OK;
+  return dconv_wgrad_cl_impl(x, g, gw, gb, workspace, B, H, W, Cin, Cout, kh, kw, dil_w, dtype, stream, true);
 }
 
+// out: family (0: dconv_wgrad_kernel, 1: dconv_wgrad3_kernel), TW, wt, otile, wsplit, nchunks, cpw, groups, LDS bytes, grid x, y, z (see the header)
+extern "C" int mv_dconv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int dtype, int* out) {
+  MV_CHECK_ARG(out);
+  DconvWgradPlan pl;
+  const int rc = dconv_wgrad_plan(B, H, W, Cin, Cout, kh, kw, dil_w, dtype, 0, 0, &pl);
+  if (rc != MV_OK) return rc;
+  const int v[12] = {pl.three, pl.tw, pl.wt, pl.otile, pl.wsplit, pl.nchunks, pl.cpw, pl.groups, (int)pl.lds, pl.gx, pl.gy, pl.gz};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
+  return MV_OK;
+}
 
 // ------------------------------------------------------------------------------------------------ tap matrix (im2col of a one-channel map)
 // out[pos][tap] (16 taps per position, zero beyond kh*kw) = sc[pos + off(tap)]  (flip = 0)  or  sc[pos - off(tap)]  (flip = 1),
@@ -1829,8 +1831,7 @@ __global__ __launch_bounds__(256) void tap_matrix_kernel(const T* __restrict__ s
 
 extern "C" int mv_tap_matrix(const void* sc, void* out, int B, int H, int W, int kh, int kw, int flip, int dtype, void* stream) {
   MV_CHECK_ARG(sc && out && B > 0 && H > 0 && W > 0 && kh > 0 && kw > 0 && kh * kw <= 16 && ((uintptr_t)out & 15) == 0);
-  const long n = (long)B * H * W * 2;
-  const unsigned grid = (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
+  const unsigned grid = grid_cap((long)B * H * W * 2, 256, 8192);
   MV_DISPATCH(dtype, hipLaunchKernelGGL(tap_matrix_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)sc, (T*)out, B, H, W,
                                         kh, kw, flip));
   MV_LAUNCH_CHECK();
@@ -1893,15 +1894,18 @@ extern "C" int mv_odconvT_wgrad_mfma(const void* x_cl, const void* gp, const voi
   float* tiles = (float*)workspace;                                           // [B][2][Cin][s*Cout]
   char* wtm = (char*)(tiles + n * B);                                         // [K][2][Cin][s*Cout] in `dtype`
   float* gtm = (float*)(wtm + ((size_t)2 * n * K + 255) / 256 * 256);         // [K][2][Cin][s*Cout] fp32
-  MV_HIP(mvi_zero_async(tiles, sizeof(float) * (size_t)n * B, s));
-  // "g" operand = x (rows = input channels), "x" operand = padded gradient rows (columns = (r, o)), taps q = 0, 1
-  int rc;
-  if (dtype == MV_BF16) rc = dwgrad_launch<bf16, 2>(gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s, Tin + 1, n);
-  else rc = dwgrad_launch<f16, 2>(gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s, Tin + 1, n);
+  // "g" operand = x (rows = input channels), "x" operand = padded gradient rows (columns = (r, o)), taps q = 0, 1; per-sample tiles
+  DconvWgradPlan pl;
+  int rc = dconv_wgrad_plan(B, 1, Tin, stride * Cout, Cin, 1, 2, 1, dtype, Tin + 1, n, &pl);
   if (rc != MV_OK) return rc;
-  const int g1 = (int)((n * K + 255) / 256 > 4096 ? 4096 : (n * K + 255) / 256);
-  if (dtype == MV_BF16) hipLaunchKernelGGL(odconvT_tapmajor_kernel<bf16>, dim3(g1), dim3(256), 0, s, (const bf16*)w, (bf16*)wtm, n * K, Cin, Cout, ks, stride);
-  else hipLaunchKernelGGL(odconvT_tapmajor_kernel<f16>, dim3(g1), dim3(256), 0, s, (const f16*)w, (f16*)wtm, n * K, Cin, Cout, ks, stride);
+  MV_HIP(mvi_zero_async(tiles, sizeof(float) * (size_t)n * B, s));
+  const DwgradArgs a{gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s};
+  const unsigned g1 = grid_cap(n * K, 256, 4096);
+  MV_DISPATCH16(dtype, {
+    rc = dwgrad_run<T>(pl, a);
+    if (rc != MV_OK) return rc;
+    hipLaunchKernelGGL(odconvT_tapmajor_kernel<T>, dim3(g1), dim3(256), 0, s, (const T*)w, (T*)wtm, n * K, Cin, Cout, ks, stride);
+  });
   rc = mv_odconv_wgrad_reduce(tiles, wtm, alpha, gtm, galpha, B, K, n, dtype, stream);
   if (rc != MV_OK) return rc;
   hipLaunchKernelGGL(odconvT_tapmajor_inv_kernel, dim3(g1), dim3(256), 0, s, gtm, gw, n * K, Cin, Cout, ks, stride);
@@ -1913,24 +1917,23 @@ extern "C" int mv_dfirst_fwd_cl(const void* x0, const void* w, const void* bias,
                                 int kw, float slope, int dtype, void* stream) {
   MV_CHECK_ARG(x0 && w && y && B > 0 && B <= 65535 && H > 0 && W > 0 && C1 > 0);
   const bool tiled = C1 % 8 == 0 && C1 <= 2048 && 256 % (C1 / 8) == 0 && ((uintptr_t)y & 15) == 0 &&
-                     ((kh == 3 && kw == 3) || (kh == 1 && kw == 15)) && dtype != MV_F32;
+                     ((kh == 3 && kw == 3) || (kh == 1 && kw == 15)) && (dtype == MV_BF16 || dtype == MV_F16);
   if (tiled) {
     const int WT = 1024, wsplit = cdiv(W, WT);
     const long nchunks = (long)B * H * wsplit;
     if (nchunks <= (1L << 30)) {
       const size_t lds = sizeof(float) * (size_t)kh * (WT + kw - 1);
       hipStream_t s = (hipStream_t)stream;
-#define MV_DF(TT) do { \
-        if (kh == 3) hipLaunchKernelGGL((dfirst_fwd_tiled_kernel<TT, 3, 3>), dim3((unsigned)nchunks), dim3(256), lds, s, (const TT*)x0, (const TT*)w, (const TT*)bias, (TT*)y, H, W, C1, slope, WT, wsplit); \
-        else hipLaunchKernelGGL((dfirst_fwd_tiled_kernel<TT, 1, 15>), dim3((unsigned)nchunks), dim3(256), lds, s, (const TT*)x0, (const TT*)w, (const TT*)bias, (TT*)y, H, W, C1, slope, WT, wsplit); } while (0)
-      if (dtype == MV_BF16) MV_DF(bf16); else MV_DF(f16);
-#undef MV_DF
+      MV_DISPATCH16(dtype, {
+        auto kern = kh == 3 ? dfirst_fwd_tiled_kernel<T, 3, 3> : dfirst_fwd_tiled_kernel<T, 1, 15>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(256), lds, s, (const T*)x0, (const T*)w, (const T*)bias, (T*)y, H, W, C1, slope, WT, wsplit);
+      });
       MV_LAUNCH_CHECK();
       return MV_OK;
     }
   }
   const long n = (long)H * W * C1;
-  dim3 grid((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256), B);
+  dim3 grid(grid_cap(n, 256, 8192), B);
   MV_DISPATCH(dtype, hipLaunchKernelGGL(dfirst_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)x0, (const T*)w,
                                         (const T*)bias, (T*)y, H, W, C1, kh, kw, slope));
   MV_LAUNCH_CHECK();
@@ -1944,20 +1947,16 @@ static void dfirst_dgrad_mfma(const void* g1, const void* w, void* gx0, float* w
   const long npos = (long)B * H * W;
   T* pk = reinterpret_cast<T*>(reinterpret_cast<char*>(ws) + sizeof(float) * 16 * (size_t)npos);   // 1 KB packed operator behind z
   hipLaunchKernelGGL(dfirst_dpack_kernel<T>, dim3(2), dim3(256), 0, s, (const T*)w, pk, 32, kh * kw);
-  const long groups = (npos + 15) / 16;
-  const int grid = (int)((groups + 3) / 4 > 4096 ? 4096 : (groups + 3) / 4);
-  hipLaunchKernelGGL((dhead_z_kernel<T, 32>), dim3(grid), dim3(256), 0, s, (const T*)g1, (const T*)pk, ws, npos, kh * kw);
-  hipLaunchKernelGGL(dhead_sum_kernel<T>, dim3((unsigned)((npos + 255) / 256 > 4096 ? 4096 : (npos + 255) / 256)), dim3(256), 0, s,
-                     ws, (const T*)nullptr, (T*)gx0, B, H, W, kh, kw, 1);
+  hipLaunchKernelGGL((dhead_z_kernel<T, 32>), dim3(grid_cap((npos + 15) / 16, 4, 4096)), dim3(256), 0, s, (const T*)g1, (const T*)pk, ws, npos, kh * kw);
+  hipLaunchKernelGGL(dhead_sum_kernel<T>, dim3(grid_cap(npos, 256, 4096)), dim3(256), 0, s, ws, (const T*)nullptr, (T*)gx0, B, H, W, kh, kw, 1);
 }
 
 extern "C" int mv_dfirst_dgrad_cl(const void* g1, const void* w, void* gx0, float* workspace, int B, int H, int W, int C1, int kh,
                                   int kw, int dtype, void* stream) {
   MV_CHECK_ARG(g1 && w && gx0 && B > 0 && B <= 65535 && H > 0 && W > 0 && C1 > 0);
-  if (workspace && C1 == 32 && kh * kw <= 16 && dtype != MV_F32 && ((uintptr_t)g1 & 15) == 0) {
+  if (workspace && C1 == 32 && kh * kw <= 16 && (dtype == MV_BF16 || dtype == MV_F16) && ((uintptr_t)g1 & 15) == 0) {
     // taps on the MFMA rows: z[tap][pos] = sum_o w[o][tap] g1[pos][o], then gx0[pos] = sum_tap z[tap][pos - off(tap)]
-    if (dtype == MV_BF16) dfirst_dgrad_mfma<bf16>(g1, w, gx0, workspace, B, H, W, kh, kw, (hipStream_t)stream);
-    else dfirst_dgrad_mfma<f16>(g1, w, gx0, workspace, B, H, W, kh, kw, (hipStream_t)stream);
+    MV_DISPATCH16(dtype, dfirst_dgrad_mfma<T>(g1, w, gx0, workspace, B, H, W, kh, kw, (hipStream_t)stream));
     MV_LAUNCH_CHECK();
     return MV_OK;
   }
@@ -1973,10 +1972,9 @@ extern "C" int mv_dfirst_wgrad_cl(const void* g1, const void* x0, float* gw, flo
   MV_CHECK_ARG(g1 && x0 && gw && gb && B > 0 && B <= 65535 && H > 0 && W > 0 && C1 > 0 && 256 % C1 == 0);
   MV_HIP(mvi_zero_async(gw, sizeof(float) * (size_t)C1 * kh * kw, (hipStream_t)stream));
   MV_HIP(mvi_zero_async(gb, sizeof(float) * (size_t)C1, (hipStream_t)stream));
-  if (dtype != MV_F32 && ((uintptr_t)g1 & 15) == 0) {
+  if ((dtype == MV_BF16 || dtype == MV_F16) && ((uintptr_t)g1 & 15) == 0) {
     int rc = MV_ERR_UNSUPPORTED;
-    if (dtype == MV_BF16) rc = dtap_launch<bf16>(g1, x0, gw, gb, B, H, W, C1, kh, kw, 0, kh * kw, 1, 1, (hipStream_t)stream);
-    else if (dtype == MV_F16) rc = dtap_launch<f16>(g1, x0, gw, gb, B, H, W, C1, kh, kw, 0, kh * kw, 1, 1, (hipStream_t)stream);
+    MV_DISPATCH16(dtype, rc = dtap_launch<T>(g1, x0, gw, gb, B, H, W, C1, kh, kw, 0, kh * kw, 1, 1, (hipStream_t)stream));
     if (rc == MV_OK) { MV_LAUNCH_CHECK(); return MV_OK; }
   }
   const int chunk = 1024;
@@ -2000,17 +1998,14 @@ extern "C" int mv_colsum_cl(const void* x, float* out, long rows, int C, int dty
 
 extern "C" int mv_take_channel(const void* x, void* out, long rows, int C, int c, int dtype, void* stream) {
   MV_CHECK_ARG(x && out && rows > 0 && C > 0 && c >= 0 && c < C);
-  const int grid = (int)((rows + 255) / 256 > 4096 ? 4096 : (rows + 255) / 256);
-  MV_DISPATCH(dtype, hipLaunchKernelGGL(take_channel_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)out, rows, C, c));
+  MV_DISPATCH(dtype, hipLaunchKernelGGL(take_channel_kernel<T>, dim3(grid_cap(rows, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)out, rows, C, c));
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
 
 extern "C" int mv_put_channel(const void* g, void* y, long rows, int C, int c, int dtype, void* stream) {
   MV_CHECK_ARG(g && y && rows > 0 && C > 0 && c >= 0 && c < C);
-  const long n = rows * C;
-  const int grid = (int)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
-  MV_DISPATCH(dtype, hipLaunchKernelGGL(put_channel_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)g, (T*)y, rows, C, c));
+  MV_DISPATCH(dtype, hipLaunchKernelGGL(put_channel_kernel<T>, dim3(grid_cap(rows * C, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)g, (T*)y, rows, C, c));
   MV_LAUNCH_CHECK();
   return MV_OK;
 }

@@ -438,6 +438,18 @@ int mv_dconv_pack_pad(const void* w, int param_dtype, void* packed, int Cout, in
                       int flip, int dtype, void* stream);
 int mv_dconv_cl_fwd(const void* x, const void* packed, const void* bias, const void* act_save, void* y, int B, int H,
                     int W, int Cin, int Cout, int kh, int kw, int dil_w, int act, float slope, int dtype, void* stream);
+/* What the dispatchers would do, asked without a GPU (no HIP call): the return code of mv_dconv_cl_fwd (with_head: of
+ * mv_dconv_cl_fwd_head, which ignores dil_w) / of mv_dconv_wgrad_cl and _pz for this shape with valid, aligned pointers, and for
+ * MV_OK the plan in out[0..11]:
+ *   mv_dconv_cl_fwd_plan: PS, MW, NB, CCH, NWV of dconv_cl_wide_kernel<T,PS,MW,NB,CCH,NWV> (PS = CCH = 0: the whole-Cin
+ *     dconv_cl_kernel<T,NWV,MW,NB>); positions, staged input channels and output rows of a workgroup; dynamic LDS bytes; grid x, y, z
+ *     (NWV * 64 threads).
+ *   mv_dconv_wgrad_plan: family (0: dconv_wgrad_kernel<T,kh,TW,WT>, 1: dconv_wgrad3_kernel<T,otile/32>), TW; WT (positions of a
+ *     chunk), otile (output channels of a tile); chunks per image row, chunks in all, chunks per workgroup, workgroups along the
+ *     positions; dynamic LDS bytes; grid x, y, z (512 threads). */
+int mv_dconv_cl_fwd_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int dtype, int with_head,
+                         int with_act_save, int* out);
+int mv_dconv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int dil_w, int dtype, int* out);
 /* Head (C = 256 -> 1 channel, discriminators.py:65 / :106) on MFMA with the taps on the matrix rows; 16-bit storage.
  *   mv_dhead_pack: w [1][C][kh][kw] -> forward + data-gradient operators (mv_dhead_packed_bytes).
  *   mv_dhead_fwd:  y [B][H][W] = bias[0] + conv(x [B][H][W][C]); workspace: mv_dhead_workspace_bytes (per-tap partial sums).

@@ -5,16 +5,18 @@ The kernels under test are the channels-last discriminator convolutions of csrc/
 instantiation ("arm") from the shape, so the tables below hold, for every arm a valid shape can reach, the smallest shape that selects
 it plus ragged companions that still select it.  `fwd_arm` / `wgrad_arm` restate the dispatchers' predicates in Python: they name the
 arm of a shape and give its position tile, channel chunk and workgroup split, which the tests use to place impulses on both sides of
-every boundary.  A kernel trace of the GPU test file is what shows that the named instantiations really are the ones launched.
+every boundary.  The restatement is an independent second statement on purpose: tests/test_host_disc_cases.py compares it, without a
+GPU, with what the library itself plans (mv_dconv_cl_fwd_plan, mv_dconv_wgrad_plan) over a sweep of shapes and every row below.
 
 Every input is made of small integers, so every sum is exact in fp32 in any order and every result is an integer (or a half-integer
 after LeakyReLU with slope 0.5) of at most 8 significant bits: exactly representable in bf16, fp16 and fp32.  The GPU tests can then
 ask for bit equality with the fp64 reference.
 
-Arms the dispatcher's source holds but no shape reaches (not in the tables):
-  dconv_cl_wide_kernel<T,2,4,4,64>, <T,2,4,4,32>   256-row tiles outside the nb8 form need Cin == 128, whose chunk is 128
-  dconv_cl_wide_kernel<T,{2,2,4 | 4,2,2 | 4,1,2},32>   chunk 32 needs Cin == 32, and `use` is then true only when the whole-Cin tile
-                                                   exceeds 160 KB - the same size as the chunk-32 tile, which is then refused too
+The tables hold every forward instantiation the library has: its dispatch table (dconv_fwd_arms16 / dconv_fwd_arms32 in
+csrc/disc_fused.hip) lists the 16 arms per 16-bit type and the six fp32 arms below and no others.  Two groups of chunked tiles that no
+shape can select are not instantiated: 256-row tiles with 64- or 32-channel chunks outside the nb8 form (256 rows need Cin == 128,
+whose chunk is 128), and every 8-wave tile with 32-channel chunks (chunk 32 needs Cin == 32, and `use` is then true only when the
+whole-Cin tile exceeds 160 KB - the same size as the chunk-32 tile, which is then refused too).
 """
 import functools
 from collections import namedtuple
@@ -55,7 +57,7 @@ Arm = namedtuple("Arm", "name npos cchunk rows")     # position tile along W, in
 
 
 def _whole(T, MW, NB, Cin, Cout, kh, kw, dil):
-    """dconv_launch<T,4,MW,NB>: the whole-Cin tile."""
+    """dconv_cl_kernel<T,4,MW,NB>: the whole-Cin tile."""
     xb = kh * (NB * 16 + (kw - 1) * dil) * lds_row_stride(Cin * 2, 2)
     ob = NB * 16 * (4 * MW * 16 * 2 + 16)
     if max(xb, ob) > LDS_MAX or Cin * 2 // 16 > 256:
@@ -64,7 +66,7 @@ def _whole(T, MW, NB, Cin, Cout, kh, kw, dil):
 
 
 def fwd_arm(B, H, W, Cin, Cout, kh, kw, dil, dtype):
-    """The instantiation dconv_cl_fwd_impl launches for this shape (mv_dconv_cl_fwd: no fused head), or Refused(code)."""
+    """The instantiation dconv_fwd_plan names for this shape (mv_dconv_cl_fwd: no fused head), or Refused(code)."""
     if not (B > 0 and H > 0 and W > 0 and Cin % 32 == 0 and Cout % 16 == 0 and kh & 1 and kw & 1):
         raise Refused(MV_ERR_ARG)
     if not (dil >= 1 and (kw - 1) * dil <= 128):
@@ -128,6 +130,13 @@ def _split(nchunks, tiles):
 def wgrad_arm(B, H, W, Cin, Cout, kh, kw, dil, dtype):
     """The instantiation mv_dconv_wgrad_cl / _pz launch, with its chunking: a chunk is WT positions of one image row, a workgroup
     (blockIdx.z) owns `cpw` consecutive chunks and keeps its accumulators across them."""
+    arm = _wgrad_arm(B, H, W, Cin, Cout, kh, kw, dil, dtype)
+    if arm.nchunks > 2 ** 30 or (arm.rows_fastest and B * arm.wsplit * (H + 2) > 2 ** 30):     # the kernels index chunks and staged rows with an int
+        raise Refused(MV_ERR_UNSUPPORTED)
+    return arm
+
+
+def _wgrad_arm(B, H, W, Cin, Cout, kh, kw, dil, dtype):
     if not (B > 0 and H > 0 and W > 0 and Cin % 8 == 0 and Cout % 8 == 0 and dil >= 1):
         raise Refused(MV_ERR_ARG)
     if dtype == MV_F32:

@@ -437,6 +437,18 @@ def test_weight_gradient_refusals_leave_the_outputs_alone(L):
             assert bool((gw == SENT).all()) and bool((gb == SENT).all()) and bool((ws == SENT).all()), (entry, why)
 
 
+def test_fp32_weight_gradient_refusal_is_decided_before_any_fill(L):
+    """fp32 3x3 with dil_w = 2 at the smallest shape: MV_ERR_UNSUPPORTED, with workspace and gb untouched - the plan is asked before
+    the zero fills for fp32 as for 16-bit storage."""
+    c = D.Case("", 1, 1, 8, 8, 8, 3, 3, 2, MV_F32)
+    x = filled((1, 1, 8, 8), MV_F32, 1.0)
+    n = 8 * 8 * 9
+    gw, gb, ws = filled((n,), torch.float32, SENT), filled((8,), torch.float32, SENT), filled((n + 8,), torch.float32, SENT)
+    assert _wgrad_call(L, "mv_dconv_wgrad_cl", x, x, gw, gb, ws, c) == D.MV_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((gw == SENT).all()) and bool((gb == SENT).all()) and bool((ws == SENT).all())
+
+
 def test_head_pack_refusals(L):
     w = torch.zeros(512 * 16, device="cuda")
     out = filled((L.mv_dhead_packed_bytes(512, MV_F32),), torch.uint8, 0x5A)

@@ -1,6 +1,9 @@
-"""Host checks of tests/disc_cases.py (no GPU): the tables name the arm the dispatcher restatement selects, every reachable arm has a
-row, the ragged-split rows really split raggedly, and - what keeps the exact GPU tests exact - the fp64 reference of every row's
-generated inputs is unchanged by a round trip through bf16 and fp16, with exactly 8 non-zero channels per input position."""
+"""Host checks of tests/disc_cases.py (no GPU): the tables name the arm the dispatcher restatement selects, the restatement agrees
+with the library's own plan queries (mv_dconv_cl_fwd_plan, mv_dconv_wgrad_plan: pure host code), every reachable arm has a row, the
+ragged-split rows really split raggedly, and - what keeps the exact GPU tests exact - the fp64 reference of every row's generated
+inputs is unchanged by a round trip through bf16 and fp16, with exactly 8 non-zero channels per input position."""
+import ctypes
+
 import pytest
 import torch
 
@@ -9,20 +12,133 @@ import disc_cases as D
 FWD_SHAPES = sorted({D.shape_of(c) for c in D.FWD_CASES})
 WG_SHAPES = sorted({D.shape_of(c) for c in D.WGRAD_CASES})
 
+ALL_DT = (D.MV_BF16, D.MV_F16, D.MV_F32)
+FWD_GEOMS = ((1, 1, 1), (1, 3, 1), (1, 15, 1), (3, 3, 1), (3, 3, 2), (3, 3, 58))
+WG_GEOMS = [(3, 3, 1)] + [(1, k, d) for k in (1, 3, 5, 7, 9, 11, 15) for d in (1, 4, 5)]
+# the training shapes of the two discriminator families (B = 64 clips of 8192 samples) and the arms their profiles show; refused shapes
+KNOWN_FWD = (((64, 2, 4096, 128, 256, 3, 3, 1), "dconv_cl_wide_kernel<bf16,1,4,8,64,4>"),
+             ((64, 2, 4096, 256, 128, 3, 3, 1), "dconv_cl_wide_kernel<bf16,1,4,8,32,2>"),
+             ((64, 1, 8192, 128, 256, 1, 15, 1), "dconv_cl_kernel<bf16,4,4,8>"),
+             ((64, 1, 8192, 256, 128, 1, 15, 1), "dconv_cl_wide_kernel<bf16,2,2,4,128,8>"),
+             ((64, 1, 8192, 64, 32, 1, 15, 1), "dconv_cl_wide_kernel<bf16,4,1,2,64,8>"))
+BAD_FWD = (((1, 1, 8, 48, 32, 1, 3, 1), D.MV_ERR_ARG), ((1, 1, 8, 32, 32, 1, 4, 1), D.MV_ERR_ARG), ((1, 1, 8, 32, 32, 1, 3, 65), D.MV_ERR_ARG))
+BAD_WG = ((1, 2, 8, 64, 64, 3, 3, 2), (1, 1, 8, 64, 64, 1, 15, 5), (1, 1, 8, 64, 64, 1, 9, 1))
+# more than 2^30 chunks (every weight-gradient kernel indexes them with an int), and the issue's small fp32 refusal
+HUGE_WG = ((65536, 65536, 8, 8, 8, 3, 3, 1), (65536, 65536, 8, 8, 8, 1, 15, 1), (1, 1, 8, 8, 8, 3, 3, 2))
+
+
+def _grid(geoms):
+    for B, H in ((1, 1), (1, 2), (12, 11), (24, 11)):
+        for W in (5, 130, 300):
+            for Cin in (24, 32, 64, 96, 128, 192, 256):
+                for Cout in (16, 32, 64, 128, 160, 192, 256, 384):
+                    for kh, kw, dil in geoms:
+                        yield B, H, W, Cin, Cout, kh, kw, dil
+
+
 def _sweep(arm_fn, dtypes, geoms):
     """Every arm name the dispatcher restatement returns over a grid of valid shapes."""
     names = set()
     for dt in dtypes:
-        for B, H in ((1, 1), (1, 2), (12, 11), (24, 11)):
-            for W in (5, 130, 300):
-                for Cin in (24, 32, 64, 96, 128, 192, 256):
-                    for Cout in (16, 32, 64, 128, 160, 192, 256, 384):
-                        for kh, kw, dil in geoms:
-                            try:
-                                names.add(arm_fn(B, H, W, Cin, Cout, kh, kw, dil, dt).name)
-                            except D.Refused:
-                                pass
+        for shape in _grid(geoms):
+            try:
+                names.add(arm_fn(*shape, dt).name)
+            except D.Refused:
+                pass
     return names
+
+
+@pytest.fixture(scope="module")
+def L():
+    from hifigan_modified import _native
+    return _native.lib()
+
+
+def _c_fwd(L, shape, dt, head=0, save=0):
+    """mv_dconv_cl_fwd_plan: (return code, arm name, the 12 plan ints)."""
+    out = (ctypes.c_int * 12)()
+    rc = L.mv_dconv_cl_fwd_plan(*shape, dt, head, save, out)
+    ps, mw, nb, cch, nwv = out[:5]
+    T = D.DT_NAME.get(dt)
+    return rc, (f"dconv_cl_wide_kernel<{T},{ps},{mw},{nb},{cch},{nwv}>" if ps else f"dconv_cl_kernel<{T},{nwv},{mw},{nb}>"), list(out)
+
+
+def _same_fwd(L, shape, dt):
+    """The C++ plan against the restatement for one shape: the refusal code, or the arm with its tile; returns the arm's name."""
+    rc, name, v = _c_fwd(L, shape, dt)
+    try:
+        arm = D.fwd_arm(*shape, dt)
+    except D.Refused as e:
+        assert rc == e.code, (shape, dt, rc, e.code)
+        return None
+    B, H, W, _, Cout = shape[:5]
+    assert rc == 0 and (name, v[5], v[6], v[7]) == tuple(arm), (shape, dt, rc, name, v, arm)
+    assert v[8] <= D.LDS_MAX and v[9:] == [D.cdiv(W, arm.npos), D.cdiv(Cout, arm.rows), B * H], (shape, dt, v)
+    return name
+
+
+def _same_wgrad(L, shape, dt):
+    out = (ctypes.c_int * 12)()
+    rc = L.mv_dconv_wgrad_plan(*shape, dt, out)
+    try:
+        arm = D.wgrad_arm(*shape, dt)
+    except D.Refused as e:
+        assert rc == e.code, (shape, dt, rc, e.code)
+        return None
+    three, tw, wt, otile = out[:4]
+    T = D.DT_NAME[dt]
+    name = f"dconv_wgrad3_kernel<{T},{otile // 32}>" if three else f"dconv_wgrad_kernel<{T},{shape[5]},{tw},{wt}>"
+    assert rc == 0 and (name, wt, otile) + tuple(out[4:8]) == tuple(arm)[:7], (shape, dt, rc, name, list(out), arm)
+    assert out[8] <= D.LDS_MAX and list(out[9:]) == [D.cdiv(shape[3], 64), D.cdiv(shape[4], otile), arm.groups], (shape, dt, list(out))
+    return name
+
+
+def test_plan_queries_agree_with_the_restatement(L):
+    """mv_dconv_cl_fwd_plan against fwd_arm and mv_dconv_wgrad_plan against wgrad_arm - refusal code, or instantiation, tile and
+    split - over the whole sweep grid with both geometry lists and all three storage types, every table row, and the known-answer and
+    refusal shapes.  Nothing is left out: a shape the restatement refuses must be refused by the library with the same code.  The
+    arms the library's plans name over the sweep are exactly the arms of the tables."""
+    rows_f = [(D.shape_of(c), c.dtype) for c in D.FWD_CASES + D.FWD_BASE]
+    rows_w = [(D.shape_of(c), c.dtype) for c in D.WGRAD_CASES]
+    extra = [(s, dt) for dt in ALL_DT for s in [k for k, _ in KNOWN_FWD] + [b for b, _ in BAD_FWD] + list(BAD_WG) + list(HUGE_WG)
+             + [(1, 1, 8, 64, 64, 1, 7, 1)]]
+    swept = [(s, dt) for dt in ALL_DT for s in _grid(tuple(FWD_GEOMS) + tuple(WG_GEOMS))]
+    fwd = {_same_fwd(L, s, dt) for s, dt in swept}
+    wg = {_same_wgrad(L, s, dt) for s, dt in swept}
+    for s, dt in rows_f + rows_w + extra:
+        _same_fwd(L, s, dt)
+        _same_wgrad(L, s, dt)
+    assert fwd - {None} == {c.arm for c in D.FWD_CASES} and wg - {None} == {c.arm for c in D.WGRAD_CASES}
+    for s, name in KNOWN_FWD:
+        assert _c_fwd(L, s, D.MV_BF16)[1] == name
+    for s in HUGE_WG:                                        # refused by the plan, so before any fill, for fp32 as for 16-bit storage
+        for dt in ALL_DT:
+            assert _same_wgrad(L, s, dt) is None and L.mv_dconv_wgrad_plan(*s, dt, (ctypes.c_int * 12)()) == D.MV_ERR_UNSUPPORTED
+    assert L.mv_dconv_cl_fwd_plan(1, 1, 8, 32, 32, 1, 3, 1, 7, 0, 0, (ctypes.c_int * 12)()) == D.MV_ERR_DTYPE
+
+
+def test_fused_head_plans_have_256_row_workgroups(L):
+    """mv_dconv_cl_fwd_head (dilation 1, no act_save) over the sweep: an accepted plan has 256 output rows per workgroup - the head
+    needs the whole 256-channel output tile - and every shape the forward itself takes is otherwise MV_ERR_UNSUPPORTED.  The head adds
+    no instantiation of its own."""
+    arms, accepted = set(), 0
+    for dt in ALL_DT:
+        for shape in _grid(((1, 1, 1), (1, 3, 1), (1, 15, 1), (3, 3, 1))):
+            rc, name, v = _c_fwd(L, shape, dt, head=1)
+            try:
+                D.fwd_arm(*shape, dt)
+            except D.Refused as e:
+                if e.code == D.MV_ERR_ARG:
+                    assert rc == D.MV_ERR_ARG, (shape, dt, rc)
+                    continue
+            if rc == 0:
+                assert v[7] == 256 and shape[4] == 256 and dt != D.MV_F32, (shape, dt, v)
+                arms.add(name)
+                accepted += 1
+            else:
+                assert rc == D.MV_ERR_UNSUPPORTED, (shape, dt, rc)
+            assert _c_fwd(L, shape, dt, head=1, save=1)[0] == D.MV_ERR_UNSUPPORTED
+    assert accepted and arms <= {c.arm for c in D.FWD_CASES}, arms
 
 
 def test_every_row_names_the_arm_its_shape_selects():
@@ -35,9 +151,8 @@ def test_every_row_names_the_arm_its_shape_selects():
 def test_every_reachable_arm_has_rows_and_ragged_companions():
     """The tables name exactly the arms that a sweep of the dispatchers over valid shapes reaches: 16 forward arms per 16-bit type,
     the six fp32 ones, and for the weight gradient the two 3x3 forms and six 1xk kernels per 16-bit type plus the two fp32 forms."""
-    all_dt = (D.MV_BF16, D.MV_F16, D.MV_F32)
-    fwd = _sweep(D.fwd_arm, all_dt, ((1, 1, 1), (1, 3, 1), (1, 15, 1), (3, 3, 1), (3, 3, 2), (3, 3, 58)))
-    wg = _sweep(D.wgrad_arm, all_dt, [(3, 3, 1)] + [(1, k, d) for k in (1, 3, 5, 7, 9, 11, 15) for d in (1, 4, 5)])
+    fwd = _sweep(D.fwd_arm, ALL_DT, FWD_GEOMS)
+    wg = _sweep(D.wgrad_arm, ALL_DT, WG_GEOMS)
     assert len(fwd) == 2 * 16 + 6 and len(wg) == 2 * 8 + 2
     assert {c.arm for c in D.FWD_BASE} == {c.arm for c in D.FWD_CASES} == fwd
     assert {c.arm for c in D.WGRAD_CASES} == wg
@@ -62,18 +177,16 @@ def test_every_reachable_arm_has_rows_and_ragged_companions():
 def test_dispatcher_restatement_known_answers():
     """The training shapes of the two discriminator families (B = 64 clips of 8192 samples) against the arms their profiles show."""
     bf = D.MV_BF16
-    assert D.fwd_arm(64, 2, 4096, 128, 256, 3, 3, 1, bf).name == "dconv_cl_wide_kernel<bf16,1,4,8,64,4>"
-    assert D.fwd_arm(64, 2, 4096, 256, 128, 3, 3, 1, bf).name == "dconv_cl_wide_kernel<bf16,1,4,8,32,2>"
-    assert D.fwd_arm(64, 1, 8192, 128, 256, 1, 15, 1, bf).name == "dconv_cl_kernel<bf16,4,4,8>"
-    assert D.fwd_arm(64, 1, 8192, 256, 128, 1, 15, 1, bf).name == "dconv_cl_wide_kernel<bf16,2,2,4,128,8>"
-    assert D.fwd_arm(64, 1, 8192, 64, 32, 1, 15, 1, bf).name == "dconv_cl_wide_kernel<bf16,4,1,2,64,8>"
+    assert len(KNOWN_FWD) == 5
+    for shape, name in KNOWN_FWD:
+        assert D.fwd_arm(*shape, bf).name == name
     assert D.lds_row_stride(128, 2) == 160 and D.lds_row_stride(256, 2) == 288 and D.lds_row_stride(64, 2) == 96
-    for bad, code in (((1, 1, 8, 48, 32, 1, 3, 1), D.MV_ERR_ARG), ((1, 1, 8, 32, 32, 1, 4, 1), D.MV_ERR_ARG),
-                      ((1, 1, 8, 32, 32, 1, 3, 65), D.MV_ERR_ARG)):
+    assert len(BAD_FWD) == 3 and len(BAD_WG) == 3
+    for bad, code in BAD_FWD:
         with pytest.raises(D.Refused) as e:
             D.fwd_arm(*bad, bf)
         assert e.value.code == code
-    for bad in ((1, 2, 8, 64, 64, 3, 3, 2), (1, 1, 8, 64, 64, 1, 15, 5), (1, 1, 8, 64, 64, 1, 9, 1)):
+    for bad in BAD_WG + HUGE_WG:
         with pytest.raises(D.Refused) as e:
             D.wgrad_arm(*bad, bf)
         assert e.value.code == D.MV_ERR_UNSUPPORTED

@@ -1,5 +1,5 @@
 // Training-side kernels: GRC weight-fold backward, fused GAN / L1 / hinge losses (value + gradient in one pass),
-// log-mel spectrogram loss (forward + backward), flat-arena AdamW and the multi-tensor gradient gather.
+// log-mel spectrogram loss (forward + backward), flat-arena AdamW, the weight EMA on the arena and the multi-tensor gradient gather.
 //   losses:   hifigan_modified/complete_vocoder.py:89-184 (LSGAN + L1), conditioned_hifigan.py:254-267 (hinge)
 //   AdamW:    conditioned_hifigan.py:219 (torch.optim.AdamW semantics: decoupled weight decay, bias correction)
 //   mel loss: defined by this build (the reference only has placeholders)
@@ -299,6 +299,54 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   const float gscale = coef ? gscale_ * coef[0] : gscale_;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     adamw_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2, gscale);
+}
+
+// ------------------------------------------------------------------------------------------- weight EMA on the arena
+// Two streaming kernels over fp32 buffers of any length behind any 4-byte-aligned pointers (optim.ArenaEMA: the generator arena and
+// its average).  The host splits [0, n) into a scalar head of `head` elements (up to the first 16-byte boundary), `nvec` 16-byte
+// groups and a scalar tail; a work item below nvec is one group, item nvec + j is the j-th scalar element (head first, then tail).
+// nvec = 0 when the two pointers are not congruent modulo 16 bytes.  Plain vector loads and stores, no LDS, no atomics.
+__device__ __forceinline__ long ema_scalar_index(long j, long head, long nvec) { return j < head ? j : j + 4 * nvec; }
+
+// ema[i] = fmaf(w, p[i] - ema[i], ema[i]): a subtraction, then ONE fused multiply-add (two roundings per update; the tests' error
+// bound is derived from exactly this expression).  w = 1 - decay: *omd_dev when given - a captured step reads it from device memory
+// at every replay - otherwise the argument.
+__device__ __forceinline__ float ema_one(float e, float p, float w) { return fmaf(w, __fsub_rn(p, e), e); }
+
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, long head,
+                                                         long nvec, const float* __restrict__ omd_dev, float omd) {
+  const float w = omd_dev ? omd_dev[0] : omd;
+  const long items = nvec + (n - 4 * nvec), stride = (long)gridDim.x * blockDim.x;
+  float4* e4 = reinterpret_cast<float4*>(ema + head);
+  const float4* p4 = reinterpret_cast<const float4*>(p + head);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += stride) {
+    if (i < nvec) {
+      float4 e = e4[i];
+      const float4 v = p4[i];
+      e.x = ema_one(e.x, v.x, w); e.y = ema_one(e.y, v.y, w); e.z = ema_one(e.z, v.z, w); e.w = ema_one(e.w, v.w, w);
+      e4[i] = e;
+    } else {
+      const long k = ema_scalar_index(i - nvec, head, nvec);
+      ema[k] = ema_one(ema[k], p[k], w);
+    }
+  }
+}
+
+// a[i] <-> b[i] (the ranges do not overlap: refused by the entry point)
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n, long head, long nvec) {
+  const long items = nvec + (n - 4 * nvec), stride = (long)gridDim.x * blockDim.x;
+  float4* a4 = reinterpret_cast<float4*>(a + head);
+  float4* b4 = reinterpret_cast<float4*>(b + head);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += stride) {
+    if (i < nvec) {
+      const float4 x = a4[i], y = b4[i];
+      a4[i] = y; b4[i] = x;
+    } else {
+      const long k = ema_scalar_index(i - nvec, head, nvec);
+      const float x = a[k], y = b[k];
+      a[k] = y; b[k] = x;
+    }
+  }
 }
 
 // gather many gradient tensors (any storage type, given per tensor) into one flat fp32 buffer: flat[dst_off + i] = src[i], a NULL
@@ -678,6 +726,42 @@ extern "C" int mv_adamw_flat_clip(float* p, const float* g, float* m, float* v, 
                                   const float* coef_dev, void* stream) {
   MV_CHECK_ARG(p && g && m && v && n > 0 && coef_dev && (step_dev || step >= 1));
   return adamw_launch(p, g, m, v, n, hparams_dev, step_dev, lr, beta1, beta2, eps, weight_decay, step, grad_scale, coef_dev, stream);
+}
+
+// The head / body / tail split of ema_update_kernel and swap_kernel: 16-byte groups only when a and b reach a 16-byte boundary at the
+// same element (arena buffers always do, at element 0).
+struct PairSplit { long head, nvec; };
+static PairSplit pair_split(const float* a, const float* b, long n) {
+  if ((((uintptr_t)a ^ (uintptr_t)b) & 15) != 0) return {0, 0};
+  long head = (long)(((16 - ((uintptr_t)a & 15)) & 15) / sizeof(float));
+  if (head > n) head = n;
+  return {head, (n - head) / 4};
+}
+static bool ranges_overlap(const float* a, const float* b, long n) {
+  const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+  return ua < ub + len && ub < ua + len;
+}
+
+extern "C" int mv_ema_update(float* ema, const float* p, long n, const float* omd_dev, float omd, void* stream) {
+  MV_CHECK_ARG(n >= 0);
+  if (n == 0) return MV_OK;            // (an empty range has no address to speak of)
+  MV_CHECK_ARG(ema && p && (((uintptr_t)ema | (uintptr_t)p | (uintptr_t)omd_dev) & 3) == 0 && !ranges_overlap(ema, p, n));
+  const PairSplit s = pair_split(ema, p, n);
+  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(s.nvec + (n - 4 * s.nvec), 256, 4096)), dim3(256), 0, (hipStream_t)stream, ema, p,
+                     n, s.head, s.nvec, omd_dev, omd);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
+}
+
+extern "C" int mv_swap_f32(float* a, float* b, long n, void* stream) {
+  MV_CHECK_ARG(n >= 0);
+  if (n == 0) return MV_OK;
+  MV_CHECK_ARG(a && b && (((uintptr_t)a | (uintptr_t)b) & 3) == 0 && !ranges_overlap(a, b, n));
+  const PairSplit s = pair_split(a, b, n);
+  hipLaunchKernelGGL(swap_kernel, dim3(grid_for(s.nvec + (n - 4 * s.nvec), 256, 4096)), dim3(256), 0, (hipStream_t)stream, a, b, n,
+                     s.head, s.nvec);
+  MV_LAUNCH_CHECK();
+  return MV_OK;
 }
 
 template <bool ACC>

@@ -13,6 +13,7 @@ output-only "feature matching" L1 to every hidden feature map of every sub-discr
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional
 
@@ -146,12 +147,21 @@ class VocoderTrainer:
     (`optimizer.grad_norm`; with `return_tensors=True` the stepping call also returns `generator_grad_norm` /
     `discriminator_grad_norm`), and a captured step follows `optimizer.max_grad_norm` at every replay.  Both need FlatAdamW
     optimizers.  With `use_graph` a window replays two graphs per input signature: "accumulate" and "accumulate + step".
-    `save_checkpoint` inside a window raises; `load_checkpoint` starts a new window."""
+    `save_checkpoint` inside a window raises; `load_checkpoint` starts a new window.
+
+    `ema_decay=d` (None, the default: no average, no launch, no checkpoint key): `trainer.ema` (optim.ArenaEMA) keeps the exponential
+    moving average of the generator's arena, updated by one streaming launch right after every generator update - once per optimizer
+    step, so once per accumulation window, eager or captured (the captured step reads this step's decay from the optimizer's state
+    block); `ema_warmup` ramps the decay as min(d, (1 + n) / (10 + n)).  Needs a FlatAdamW generator optimizer.  Under data parallel
+    every rank averages its own (identical) weights.  `with trainer.ema_weights():` runs its body with the averaged weights in the
+    generator (an exchange on entry, the same exchange on exit; no train_step inside), `evaluate(..., weights="ema" | "live")` is a
+    no-grad validation pass, and the checkpoint gains `ema_state` and `ema_generator_state_dict` (a complete generator state_dict
+    with the averaged weights: what inference loads)."""
 
     def __init__(self, vocoder: ModifiedHiFiGANVocoder, generator_optimizer=None, discriminator_optimizer=None,
                  device=None, mel_mode: str = "stft", grad_sync=None, bucket_mib: int = 8, use_graph: bool = False,
                  graph_warmup: int = 2, dropout_rng: Optional[str] = None, schedulers=(), accumulation_steps: int = 1,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True):
         from .training import GradWindow
         self.window = w = GradWindow("VocoderTrainer", accumulation_steps, max_grad_norm, grad_sync, bucket_mib)
         self.accumulation_steps, self.max_grad_norm = w.accumulation_steps, w.max_grad_norm
@@ -179,6 +189,14 @@ class VocoderTrainer:
             raise ValueError(f"VocoderTrainer: dropout_rng must be 'torch' or 'counter', got {dropout_rng!r}")
         self.dropout_rng = Fn.DropoutRNG.from_torch() if dropout_rng == "counter" else None
         self.schedulers = tuple(s for s in schedulers if s is not None)
+        self.ema = None
+        self._ema_swapped = False            # inside `with ema_weights()`: the arena holds the average, the shadow the live weights
+        if ema_decay is not None:
+            from .optim import ArenaEMA, FlatAdamW
+            if not isinstance(generator_optimizer, FlatAdamW):
+                raise ValueError("VocoderTrainer: ema_decay averages FlatAdamW's parameter arena; the generator optimizer is a "
+                                 f"{type(generator_optimizer).__name__}")
+            self.ema = ArenaEMA(generator_optimizer, ema_decay, warmup=ema_warmup)
 
     @staticmethod
     def default_optimizers(vocoder, lr=2e-4, betas=(0.8, 0.99), weight_decay=1e-4):
@@ -207,6 +225,8 @@ class VocoderTrainer:
 
     def train_step(self, mel_spectrogram, real_audio, speaker_embedding=None, emotion_embedding=None,
                    return_tensors: bool = False) -> Dict[str, float]:
+        if self._ema_swapped:
+            raise RuntimeError("VocoderTrainer.train_step inside `with ema_weights()`: the generator holds the averaged weights")
         mel_spectrogram = mel_spectrogram.to(self.device)
         real_audio = real_audio.to(self.device)
         # (a new window: both arenas start from zero, every micro-step adds)
@@ -269,6 +289,8 @@ class VocoderTrainer:
                 if defer:
                     self._apply_step(self.discriminator_optimizer, d_scale)
                 self._apply_step(self.generator_optimizer, g_scale)
+                if self.ema is not None:
+                    self.ema.update()          # once per optimizer step: only the call that steps reaches this line
         finally:
             for p in self._d_params:
                 p.requires_grad_(True)
@@ -384,8 +406,61 @@ class VocoderTrainer:
         """Host read-back of a loss dict (one device synchronisation)."""
         return {k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in losses.items()}
 
+    # ---- the averaged generator
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body with the averaged weights in the generator: one exchange of the arena and the average on entry, the same
+        exchange on exit (also when the body raises), which restores both bit for bit."""
+        if self.ema is None:
+            raise RuntimeError("VocoderTrainer.ema_weights: this trainer keeps no EMA (ema_decay=None)")
+        if self._ema_swapped:
+            raise RuntimeError("VocoderTrainer.ema_weights: already inside the block")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("VocoderTrainer.ema_weights: the exchange is not part of a captured graph")
+        self.ema.swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self.ema.swap()
+            self._ema_swapped = False
+
+    def evaluate(self, mel_spectrogram, real_audio, speaker_embedding=None, emotion_embedding=None, weights: str = "ema"):
+        """One validation pass (train_config.yaml: eval_steps): the vocoder's forward in eval mode under no_grad, with the averaged
+        ("ema") or the live generator weights; returns {"mel_loss": mel L1 of the generated waveform against the log-mel of
+        `real_audio`} as a host float.  Leaves the modules' training flags as they were and touches neither the dropout stream nor
+        the accumulation window, the optimizers or the schedules."""
+        if weights not in ("ema", "live"):
+            raise ValueError(f"VocoderTrainer.evaluate: weights must be 'ema' or 'live', got {weights!r}")
+        if weights == "ema" and self.ema is None:
+            raise RuntimeError("VocoderTrainer.evaluate: weights='ema' on a trainer that keeps no EMA (ema_decay=None)")
+        voc = self.vocoder
+        mel_spectrogram, real_audio = mel_spectrogram.to(self.device), real_audio.to(self.device)
+        modes = [(m, m.training) for m in voc.modules()]
+        voc.train(False)
+        try:
+            with torch.no_grad(), (self.ema_weights() if weights == "ema" else contextlib.nullcontext()):
+                wave = voc(mel_spectrogram, speaker_embedding, emotion_embedding)["generated_waveform"]
+                loss = Fn.mel_l1(wave, voc.log_mel(real_audio), voc.mel_fb, voc.n_fft, voc.hop)
+        finally:
+            for m, flag in modes:
+                m.training = flag
+        return {"mel_loss": float(loss)}
+
+    def ema_generator_state_dict(self):
+        """A complete generator state_dict with the arena parameters at their averaged values, every other entry live."""
+        if self._ema_swapped:
+            raise RuntimeError("VocoderTrainer: inside `with ema_weights()` the arena and the average are exchanged")
+        gen = self.vocoder.generator
+        sd = {k: v.detach().clone() for k, v in gen.state_dict().items()}
+        for name, view in self.ema.named_tensors(gen):
+            sd[name] = view.clone()
+        return sd
+
     def save_checkpoint(self, path: str):
         self.window.assert_boundary("VocoderTrainer.save_checkpoint")
+        if self._ema_swapped:
+            raise RuntimeError("VocoderTrainer.save_checkpoint inside `with ema_weights()`: the generator holds the averaged weights")
         ck = {"vocoder_state_dict": self.vocoder.state_dict(),
               # torch.optim.AdamW's layout, so the reference's own load path (complete_vocoder.py:463-468) reads the file too
               "generator_optimizer_state_dict": self.generator_optimizer.torch_state_dict(),
@@ -398,9 +473,14 @@ class VocoderTrainer:
         if self.vocoder.fm_mode != "output":             # (a default trainer's file keeps the reference's keys)
             ck["fm_mode"] = self.vocoder.fm_mode
         ck.update(self.window.checkpoint_extras())
+        if self.ema is not None:
+            ck["ema_state"] = self.ema.state_dict()
+            ck["ema_generator_state_dict"] = self.ema_generator_state_dict()
         torch.save(ck, path)
 
     def load_checkpoint(self, path: str):
+        if self._ema_swapped:
+            raise RuntimeError("VocoderTrainer.load_checkpoint inside `with ema_weights()`")
         ck = torch.load(path, map_location=self.device, weights_only=True)
         self.vocoder.load_state_dict(ck["vocoder_state_dict"])
         self.generator_optimizer.load_state_dict(ck["generator_optimizer_state_dict"])
@@ -411,3 +491,8 @@ class VocoderTrainer:
             sch.load_state_dict(sd)
         self.vocoder.set_feature_matching(ck.get("fm_mode", "output"))     # (no key: the reference's term)
         self.window.reset()                  # a checkpoint is always a window boundary
+        if self.ema is not None:             # (a file's EMA keys mean nothing to a trainer without one)
+            if "ema_state" in ck:
+                self.ema.load_state_dict(ck["ema_state"])
+            else:                            # a file from a trainer without EMA: the average starts over from the loaded weights
+                self.ema.reset()

@@ -82,6 +82,7 @@ class FlatAdamW:
         #                                      in a step is left untouched, so its bias correction lags the others'
         self._n_all = len(params)            # parameters a torch.optim optimizer would enumerate (param_groups[0]['params'])
         self._capture = None                 # state of a captured training step (capture_begin / capture_end)
+        self.ema = None                      # the ArenaEMA averaging this arena, if any (it attaches itself)
         # 16-bit shadows of the arena (one per activation dtype in use): refreshed by ONE cast launch per optimizer step, so
         # the ~200 per-parameter casts of a training step disappear; ops._ParamCache hands out views of them
         self._shadows = {}
@@ -271,7 +272,8 @@ class FlatAdamW:
         """Call right before a training step is captured into a HIP graph (torch.cuda.graph): the gathers' descriptor tables become
         pinned and persistent, and AdamW reads its hyper-parameters and per-run step counts from a device state block (int32 words:
         0-4 fp32 {lr, beta1, beta2, eps, weight_decay}, 5 fp32 max_grad_norm (read by the gradient norm of a clipped step, 0 otherwise),
-        6-7 unused, 8 + r the count of run r) that before_replay() refreshes.  The norm and the clip coefficient themselves are
+        6 fp32 one minus the EMA decay of this step (read by ArenaEMA.update's kernel; 0 without an attached EMA), 7 unused, 8 + r the
+        count of run r) that before_replay() refreshes.  The norm and the clip coefficient themselves are
         written by the device into a buffer of their own (allocated here, before the capture).  stepping=False: the captured body
         only gathers (a micro-step inside an accumulation window) - no update, no runs, nothing to refresh."""
         dev = self.flat_p.device
@@ -282,7 +284,7 @@ class FlatAdamW:
         if self.max_grad_norm is not None:
             self._clip_slots()
         self._capture = {"keep": [], "block": block, "runs": [], "planned": planned, "pinned": pinned, "clip": False,
-                         "stepping": stepping}
+                         "stepping": stepping, "ema": False}
 
     def _planned_runs(self):
         """Runs of equal step count over ALL parameters (a captured step must give every parameter of the arena a gradient)."""
@@ -295,7 +297,8 @@ class FlatAdamW:
         if cap["runs"] != cap["planned"]:
             raise RuntimeError("FlatAdamW: the captured step left parameters without a gradient: a captured step must update every "
                                "parameter of the arena")
-        return {"keep": cap["keep"], "block": cap["block"], "runs": cap["runs"], "clip": cap["clip"], "stepping": cap["stepping"]}
+        return {"keep": cap["keep"], "block": cap["block"], "runs": cap["runs"], "clip": cap["clip"], "stepping": cap["stepping"],
+                "ema": cap["ema"]}
 
     def runs_match(self, state):
         """True while the host's step counts still form the runs the captured step was recorded with (a restored state can split or
@@ -313,6 +316,8 @@ class FlatAdamW:
             if self.max_grad_norm is None or not self.max_grad_norm > 0:
                 raise RuntimeError("FlatAdamW: the captured step clips its gradient norm: max_grad_norm must stay a positive number")
             words[5:6].view(np.float32)[:] = self.max_grad_norm
+        if self.ema is not None:              # the same block, the same upload: this update's 1 - decay (warm-up moves it every step)
+            words[6:7].view(np.float32)[:] = self.ema.one_minus_decay()
         words[8:] = [self.steps[i0] + 1 for (i0, _) in state["runs"]]
         state["block"].upload(words)
 
@@ -322,6 +327,8 @@ class FlatAdamW:
             for k in range(i0, i1):
                 self.steps[k] += 1
         self.step_count = max(self.steps)
+        if state.get("ema"):                  # the replayed step contained the EMA update
+            self.ema.num_updates += 1
         ops.bump_param_epoch(self)
         self._shadow_state = (self._state_epoch(), [p._version for p in self.params])   # the replay refreshed the shadows itself
 
@@ -401,6 +408,75 @@ class FlatAdamW:
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
+
+
+class ArenaEMA:
+    """Exponential moving average of one FlatAdamW arena (the generator's weights): `shadow`, an fp32 buffer laid out like
+    `opt.flat_p`, follows it by ONE streaming launch per optimizer step (mv_ema_update: shadow += w * (flat_p - shadow), w = 1 - decay).
+    warmup: the decay of update number n (from 0) is min(decay, (1 + n) / (10 + n)), so the average leaves its initial value quickly
+    and only later becomes slow; formed on the host in Python floats, w = float32(1 - that).  Inside a captured step the kernel reads
+    w from word 6 of the optimizer's state block, which FlatAdamW.before_replay refreshes with the rest of the block; the host's
+    `num_updates` moves in after_replay.  The arena's padding words are averaged too: zeros on both sides."""
+
+    def __init__(self, opt, decay, warmup=True):
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating)) or not 0.0 < decay < 1.0:
+            raise ValueError(f"ArenaEMA: decay must be a number in (0, 1), got {decay!r}")
+        self.opt, self.decay, self.warmup = opt, float(decay), bool(warmup)
+        self.shadow = torch.empty(opt.numel, device=opt.flat_p.device, dtype=torch.float32)
+        self.reset()
+        opt.ema = self
+
+    def reset(self):
+        """The average starts over from the arena's current weights."""
+        self.shadow.copy_(self.opt.flat_p)          # device to device
+        self.num_updates = 0
+
+    def current_decay(self):
+        """The decay the NEXT update uses."""
+        if not self.warmup:
+            return self.decay
+        return min(self.decay, (1 + self.num_updates) / (10 + self.num_updates))
+
+    def one_minus_decay(self):
+        return np.float32(1.0 - self.current_decay())
+
+    def update(self):
+        from .torch_ops import OPS
+        opt = self.opt
+        cap = opt._capture
+        if cap is None:
+            OPS.ema_update_(self.shadow, opt.flat_p, None, float(self.one_minus_decay()))
+            self.num_updates += 1
+        else:       # being captured (nothing executes now): w comes from the state block, the count moves in after_replay()
+            cap["ema"] = True
+            OPS.ema_update_(self.shadow, opt.flat_p, cap["block"].dev.view(torch.float32)[6:7], 0.0)
+
+    def swap(self):
+        """Exchange the arena and the average (one launch): the modules then compute with the averaged weights, and every cast and
+        packed weight derived from the arena follows.  Twice restores both buffers bit for bit."""
+        from .torch_ops import OPS
+        OPS.swap_(self.opt.flat_p, self.shadow)
+        ops.bump_param_epoch(self.opt)
+        self.opt._refresh_shadows()
+
+    def named_tensors(self, module=None):
+        """(name, view of the average with the parameter's shape) per arena parameter.  The names are `module`'s (named_parameters)
+        for the arena parameters it holds; without a module, the parameters' positions in the arena."""
+        if module is None:
+            names = {id(p): str(i) for i, p in enumerate(self.opt.params)}
+        else:
+            names = {id(p): n for n, p in module.named_parameters()}
+        return [(names[id(p)], self.shadow[o:o + p.numel()].view(p.shape))
+                for p, o in zip(self.opt.params, self.opt.offsets) if id(p) in names]
+
+    def state_dict(self):
+        return {"decay": self.decay, "warmup": self.warmup, "num_updates": self.num_updates, "shadow": self.shadow.clone()}
+
+    def load_state_dict(self, sd):
+        if sd["shadow"].numel() != self.shadow.numel():
+            raise ValueError(f"ArenaEMA: a shadow of {sd['shadow'].numel()} elements does not fit an arena of {self.shadow.numel()}")
+        self.decay, self.warmup, self.num_updates = float(sd["decay"]), bool(sd["warmup"]), int(sd["num_updates"])
+        self.shadow.copy_(sd["shadow"].reshape(-1))
 
 
 class WarmupCosineLR:

@@ -22,6 +22,7 @@ Operators (schemas as registered; ``act``: 0 none, 1 LeakyReLU, 2 tanh, 3 SiLU; 
   fused_adamw_, fused_adamw_dev_, fused_adamw_hp_, fused_adamw_clip_   conditioned_hifigan.py:219 (torch.optim.AdamW semantics): one
                                                      kernel, the per-step inputs by value or from device memory, clipped or not
   multi_gather_acc_, zero_, grad_norm                gradient_accumulation_steps / max_grad_norm of configs/*train_config.yaml
+  ema_update_, swap_                                 the generator's weight EMA on the arena (optim.ArenaEMA)
 """
 from __future__ import annotations
 
@@ -300,6 +301,23 @@ def _install():
         N.call("mv_grad_norm", _ptr(g), g.numel(), float(pre_scale), _ptr(max_norm_dev), float(max_norm), c_void_p(out.data_ptr() + 8),
                _ptr(out), ops._stream())
     _inplace("grad_norm", "(Tensor g, Tensor(a!) out, Tensor? max_norm_dev, float max_norm, float pre_scale) -> ()", grad_norm)
+
+    # ---- weight EMA on the arena (optim.ArenaEMA): ema += w * (p - ema), w = 1 - decay from omd_dev (one fp32 element on the GPU: what a
+    # captured step replays) or, with None, the float argument; and the exchange of two buffers (the average in the live weights' place)
+    def _check_pair(name, a, b):
+        if any(t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda for t in (a, b)) or a.numel() != b.numel():
+            raise RuntimeError(f"{NS}::{name}: both tensors must be contiguous fp32 GPU tensors of one size")
+
+    def ema_update_(ema, p, omd_dev, omd):
+        _check_pair("ema_update_", ema, p)
+        _check_one("ema_update_", "omd_dev", omd_dev, torch.float32)
+        N.call("mv_ema_update", _ptr(ema), _ptr(p), ema.numel(), _ptr(omd_dev), float(omd), ops._stream())
+    _inplace("ema_update_", "(Tensor(a!) ema, Tensor p, Tensor? omd_dev, float omd) -> ()", ema_update_)
+
+    def swap_(a, b):
+        _check_pair("swap_", a, b)
+        N.call("mv_swap_f32", _ptr(a), _ptr(b), a.numel(), ops._stream())       # overlapping ranges: MV_ERR_ARG, nothing is launched
+    _inplace("swap_", "(Tensor(a!) a, Tensor(b!) b) -> ()", swap_)
 
 
 def _install_fakes():

@@ -396,6 +396,15 @@ int mv_adamw_flat_clip(float* p, const float* g, float* m, float* v, long n, con
                        float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, const float* coef_dev,
                        void* stream);
 
+/* Exponential moving average of an fp32 arena (the generator's weights: optim.ArenaEMA) and the exchange that puts the average in
+ * the live weights' place for an evaluation.  Both stream over any n >= 0 behind any 4-byte-aligned pointers: 16-byte loads and
+ * stores on the body when the two pointers are congruent modulo 16 bytes, scalar head and tail; n = 0 launches nothing.
+ *   mv_ema_update: ema[i] = fmaf(w, p[i] - ema[i], ema[i]), w = 1 - decay = omd_dev[0] when omd_dev is given (device fp32: a captured
+ *     training step reads it at every replay), otherwise `omd`.  Overlapping ema / p: MV_ERR_ARG.
+ *   mv_swap_f32: a[i] <-> b[i]; twice restores both.  Overlapping ranges or n < 0: MV_ERR_ARG, nothing is launched. */
+int mv_ema_update(float* ema, const float* p, long n, const float* omd_dev, float omd, void* stream);
+int mv_swap_f32(float* a, float* b, long n, void* stream);
+
 /* uint8 keep-mask of nn.Dropout(p) (grc_lora.py:151,162): mask[i] = 1 with probability 1-p, Philox4x32-10 keyed by `seed`,
  * counter = element index / 8 (16 random bits per element; resolution 2^-16 on p). */
 int mv_dropout_mask(uint8_t* mask, long n, float p, long seed, void* stream);

@@ -1,7 +1,8 @@
 """Timing of one full training step (variant B: G fwd -> D step -> G step) at a given batch.
-usage: bench_train.py [B] [mel frames] [fp32|bf16|fp16] [--graph] [--accum N] [--max-grad-norm X] [--fm MODE] [--steps K] [--warmup W]
+usage: bench_train.py [B] [mel frames] [fp32|bf16|fp16] [--graph] [--accum N] [--max-grad-norm X] [--fm MODE] [--ema DECAY] [--steps K] [--warmup W]
 --graph: the captured step (VocoderTrainer(use_graph=True)); --accum / --max-grad-norm: the trainer's accumulation_steps / max_grad_norm;
---fm output|features: the vocoder's feature-matching mode (set_feature_matching).
+--fm output|features: the vocoder's feature-matching mode (set_feature_matching); --ema DECAY: the trainer's ema_decay (the generator's
+weight EMA, one more streaming launch per optimizer step).
 The time is per train_step CALL (with --accum N an optimizer step is N calls); the last line is one JSON object."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +19,7 @@ ap.add_argument("--graph", action="store_true")
 ap.add_argument("--accum", type=int, default=1)
 ap.add_argument("--max-grad-norm", type=float, default=None)
 ap.add_argument("--fm", default="output", choices=["output", "features"])
+ap.add_argument("--ema", type=float, default=None)
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=2)
 a = ap.parse_args()
@@ -32,6 +34,8 @@ if a.accum != 1:
     kw["accumulation_steps"] = a.accum
 if a.max_grad_norm is not None:
     kw["max_grad_norm"] = a.max_grad_norm
+if a.ema is not None:
+    kw["ema_decay"] = a.ema
 tr = H.VocoderTrainer(voc, device=torch.device("cuda"), **kw)
 mel = torch.randn(B, 80, Tm, device="cuda").to(dt)
 real = torch.randn(B, 1, Tm * 256, device="cuda").clamp(-1, 1).to(dt)
@@ -48,5 +52,5 @@ for i in range(n):
 torch.cuda.synchronize()
 dtm = (time.perf_counter() - t0) / n
 print(f"B={B} T={Tm*256} {dt}: {dtm*1e3:.1f} ms/step  -> {B*Tm*256/dtm:,.0f} samples/s")
-print(json.dumps({"B": B, "samples": Tm * 256, "dtype": a.dtype, "graph": a.graph, "accum": a.accum, "max_grad_norm": a.max_grad_norm, "fm": a.fm,
+print(json.dumps({"B": B, "samples": Tm * 256, "dtype": a.dtype, "graph": a.graph, "accum": a.accum, "max_grad_norm": a.max_grad_norm, "fm": a.fm, "ema": a.ema,
                   "calls": n, "ms_per_step": round(dtm * 1e3, 3)}))

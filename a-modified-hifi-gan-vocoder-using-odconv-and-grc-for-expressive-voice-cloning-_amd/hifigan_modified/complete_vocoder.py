@@ -9,7 +9,8 @@ Differences, all documented in DESIGN.md: the generator is the one ``conditioned
 runs frozen (eval statistics, no gradient) with its one broken layer resized, see that module; the mel term is a real log-mel/STFT L1
 (``mel_mode="stft"``) instead of the reference's ``generated_mel = mel`` placeholder (``mel_mode="placeholder"``
 reproduces that: the term is then identically zero); `fm_mode="features"` (opt-in) extends the reference's
-output-only "feature matching" L1 to every hidden feature map of every sub-discriminator, HiFi-GAN's definition of the term.
+output-only "feature matching" L1 to every hidden feature map of every sub-discriminator, HiFi-GAN's definition of the term;
+`set_stft_loss` (opt-in) adds a multi-resolution STFT loss of the fake against the real waveform to the generator's total.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fn
+from . import ops
 from .discriminators import HiFiGANDiscriminators
 from .embedding_extractors import EmbeddingExtractor
 from .generator import ModifiedHiFiGANGenerator
@@ -28,10 +30,13 @@ from .mel import mel_filterbank
 
 
 FM_MODES = ("output", "features")
+STFT_DEFAULT_RESOLUTIONS = ops.STFT_DEFAULT_RESOLUTIONS     # ((512, 128), (1024, 256), (2048, 512)): (n_fft, hop)
 
 
 class ModifiedHiFiGANVocoder(nn.Module):
     fm_mode = "output"          # host state, not a parameter or buffer: set_feature_matching; the trainer's checkpoint stores it
+    stft_resolutions = None     # host state like fm_mode: set_stft_loss; None = the term is off
+    stft_weight = 1.0           # untuned
 
     def __init__(self, input_channels: int = 80, hidden_channels: int = 512,
                  speaker_embedding_dim: int = 192, emotion_embedding_dim: int = 256,
@@ -69,6 +74,26 @@ class ModifiedHiFiGANVocoder(nn.Module):
         self.fm_mode = mode
         return self
 
+    def set_stft_loss(self, resolutions=STFT_DEFAULT_RESOLUTIONS, weight: float = 1.0):
+        """Multi-resolution STFT loss in the generator's total (Yamamoto et al. 2020; off by default, `resolutions=None` turns it
+        off again): `stft_loss` = the mean over the (n_fft, hop) resolutions of spectral convergence + log-magnitude L1 of
+        `fake_audio` against `real_audio` (a constant), with the mel term's framing; the total gains weight * stft_loss.  The
+        default weight 1.0 is untuned.  The definition and what is supported: mv_stft_loss in the header; ValueError names a
+        resolution that is not."""
+        if resolutions is None:
+            self.stft_resolutions = None
+        else:
+            self.stft_resolutions = ops.stft_resolutions(resolutions)
+        self.stft_weight = float(weight)
+        return self
+
+    @property
+    def stft_config(self):
+        """None when the term is off, else {"resolutions": [[n_fft, hop], ...], "weight": w} (plain lists: what a checkpoint stores)."""
+        if self.stft_resolutions is None:
+            return None
+        return {"resolutions": [list(r) for r in self.stft_resolutions], "weight": self.stft_weight}
+
     def get_discriminator_outputs(self, real_audio, fake_audio):
         return self.discriminators(real_audio, fake_audio)
 
@@ -102,8 +127,12 @@ class ModifiedHiFiGANVocoder(nn.Module):
         else:
             mel_loss = Fn.l1(generated_mel, mel_spectrogram)
         total = mpd_loss + msd_loss + self.fm_weight * (mpd_fm + msd_fm) + self.mel_weight * mel_loss
-        return {"total_loss": total, "mpd_loss": mpd_loss, "msd_loss": msd_loss, "mpd_fm_loss": mpd_fm,
-                "msd_fm_loss": msd_fm, "mel_loss": mel_loss}
+        losses = {"total_loss": total, "mpd_loss": mpd_loss, "msd_loss": msd_loss, "mpd_fm_loss": mpd_fm,
+                  "msd_fm_loss": msd_fm, "mel_loss": mel_loss}
+        if self.stft_resolutions is not None:
+            losses["stft_loss"] = Fn.mr_stft_loss(fake_audio, real_audio, self.stft_resolutions)
+            losses["total_loss"] = total + self.stft_weight * losses["stft_loss"]
+        return losses
 
     def compute_discriminator_losses(self, real_audio, fake_audio):
         out = self.discriminators(real_audio, fake_audio)
@@ -156,7 +185,10 @@ class VocoderTrainer:
     every rank averages its own (identical) weights.  `with trainer.ema_weights():` runs its body with the averaged weights in the
     generator (an exchange on entry, the same exchange on exit; no train_step inside), `evaluate(..., weights="ema" | "live")` is a
     no-grad validation pass, and the checkpoint gains `ema_state` and `ema_generator_state_dict` (a complete generator state_dict
-    with the averaged weights: what inference loads)."""
+    with the averaged weights: what inference loads).
+
+    `vocoder.set_stft_loss(...)` (off by default): the step's result, `evaluate()` and the checkpoint gain `stft_loss` only while the
+    term is on, and a captured step records one graph per configuration of it."""
 
     def __init__(self, vocoder: ModifiedHiFiGANVocoder, generator_optimizer=None, discriminator_optimizer=None,
                  device=None, mel_mode: str = "stft", grad_sync=None, bucket_mib: int = 8, use_graph: bool = False,
@@ -295,8 +327,11 @@ class VocoderTrainer:
             for p in self._d_params:
                 p.requires_grad_(True)
         self.last_losses = (g_losses, d_losses)
-        return {"generator_loss": g_losses["total_loss"], "discriminator_loss": d_losses["total_loss"],
-                "mel_loss": g_losses["mel_loss"]}
+        res = {"generator_loss": g_losses["total_loss"], "discriminator_loss": d_losses["total_loss"],
+               "mel_loss": g_losses["mel_loss"]}
+        if "stft_loss" in g_losses:
+            res["stft_loss"] = g_losses["stft_loss"]
+        return res
 
     # ---- captured step
     def _graph_ok(self):
@@ -313,6 +348,8 @@ class VocoderTrainer:
         key = sig if self.accumulation_steps == 1 else sig + ("step" if do_step else "accumulate",)
         if self.vocoder.fm_mode != "output":
             key = key + (("fm", self.vocoder.fm_mode),)    # a mode change after a capture records its own graph
+        if self.vocoder.stft_resolutions is not None:      # (likewise: the resolutions and the weight are baked into the launches)
+            key = key + (("stft", self.vocoder.stft_resolutions, self.vocoder.stft_weight),)
         st = self._graphs.get(key)
         if st is None:
             st = self._graphs[key] = {"warm": 0, "graph": None}
@@ -428,7 +465,7 @@ class VocoderTrainer:
     def evaluate(self, mel_spectrogram, real_audio, speaker_embedding=None, emotion_embedding=None, weights: str = "ema"):
         """One validation pass (train_config.yaml: eval_steps): the vocoder's forward in eval mode under no_grad, with the averaged
         ("ema") or the live generator weights; returns {"mel_loss": mel L1 of the generated waveform against the log-mel of
-        `real_audio`} as a host float.  Leaves the modules' training flags as they were and touches neither the dropout stream nor
+        `real_audio`} as a host float, and next to it "stft_loss" while that term is on.  Leaves the modules' training flags as they were and touches neither the dropout stream nor
         the accumulation window, the optimizers or the schedules."""
         if weights not in ("ema", "live"):
             raise ValueError(f"VocoderTrainer.evaluate: weights must be 'ema' or 'live', got {weights!r}")
@@ -442,10 +479,11 @@ class VocoderTrainer:
             with torch.no_grad(), (self.ema_weights() if weights == "ema" else contextlib.nullcontext()):
                 wave = voc(mel_spectrogram, speaker_embedding, emotion_embedding)["generated_waveform"]
                 loss = Fn.mel_l1(wave, voc.log_mel(real_audio), voc.mel_fb, voc.n_fft, voc.hop)
+                stft = None if voc.stft_resolutions is None else Fn.mr_stft_loss(wave, real_audio, voc.stft_resolutions)
         finally:
             for m, flag in modes:
                 m.training = flag
-        return {"mel_loss": float(loss)}
+        return {"mel_loss": float(loss)} if stft is None else {"mel_loss": float(loss), "stft_loss": float(stft)}
 
     def ema_generator_state_dict(self):
         """A complete generator state_dict with the arena parameters at their averaged values, every other entry live."""
@@ -472,6 +510,8 @@ class VocoderTrainer:
             ck["scheduler_state_dicts"] = [s.state_dict() for s in self.schedulers]
         if self.vocoder.fm_mode != "output":             # (a default trainer's file keeps the reference's keys)
             ck["fm_mode"] = self.vocoder.fm_mode
+        if self.vocoder.stft_config is not None:
+            ck["stft_loss"] = self.vocoder.stft_config
         ck.update(self.window.checkpoint_extras())
         if self.ema is not None:
             ck["ema_state"] = self.ema.state_dict()
@@ -490,6 +530,8 @@ class VocoderTrainer:
         for sch, sd in zip(self.schedulers, ck.get("scheduler_state_dicts", ())):
             sch.load_state_dict(sd)
         self.vocoder.set_feature_matching(ck.get("fm_mode", "output"))     # (no key: the reference's term)
+        stft = ck.get("stft_loss")                                         # (no key: the term is off)
+        self.vocoder.set_stft_loss(None) if stft is None else self.vocoder.set_stft_loss(stft["resolutions"], stft["weight"])
         self.window.reset()                  # a checkpoint is always a window boundary
         if self.ema is not None:             # (a file's EMA keys mean nothing to a trainer without one)
             if "ema_state" in ck:

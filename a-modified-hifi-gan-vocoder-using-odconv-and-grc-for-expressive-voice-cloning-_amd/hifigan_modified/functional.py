@@ -907,6 +907,34 @@ def mel_mse(wave, target, fb, n_fft=1024, hop=256, clampv=1e-5, weight=1.0):
     return _mel(wave, target, fb, n_fft, hop, clampv, weight, 1)
 
 
+class _StftLoss(Function):
+    """weight * multi-resolution STFT loss of fake against real (a constant); defined by this build.  Value and
+    gradient come from the same forward call (csrc/stft_loss.hip), like _MelL1."""
+
+    @staticmethod
+    def forward(ctx, fake, real, n_ffts, hops, floor, weight):
+        loss, _, gwave = ops.stft_loss(fake, real, tuple(zip(n_ffts, hops)), floor, weight, backward=fake.requires_grad)
+        ctx.save_for_backward(gwave)
+        ctx.dtype = fake.dtype
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (gwave,) = ctx.saved_tensors
+        gw = ops.scale_to(gwave, 1.0, g.reshape(1).float())
+        return (gw if ctx.dtype == torch.float32 else ops.cast(gw, ctx.dtype)), None, None, None, None, None
+
+
+def mr_stft_loss(fake, real, resolutions=ops.STFT_DEFAULT_RESOLUTIONS, floor=1e-7, weight=1.0):
+    """weight * (1/R) sum_r (spectral convergence + log-magnitude L1) of fake against real over the (n_fft, hop) resolutions; the
+    gradient goes to fake only."""
+    res = ops.stft_resolutions(resolutions)
+    n_ffts, hops = [n for n, _ in res], [h for _, h in res]
+    if DISPATCH == "torch_ops":
+        return _t().OPS.stft_loss(fake, real, n_ffts, hops, float(floor), float(weight))
+    return _StftLoss.apply(fake, real, n_ffts, hops, float(floor), float(weight))
+
+
 def mel_spectrogram(wave, fb, n_fft=1024, hop=256, clampv=1e-5):
     """log-mel [B, n_mels, T/hop] (fp32) of a waveform [B,1,T]."""
     with torch.no_grad():

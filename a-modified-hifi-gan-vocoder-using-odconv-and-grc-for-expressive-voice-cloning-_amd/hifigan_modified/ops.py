@@ -7,7 +7,7 @@ libmi355x_vocoder.so.  Inputs must live on the GPU: there is no CPU path.
 from __future__ import annotations
 
 import weakref
-from ctypes import c_void_p
+from ctypes import c_int, c_void_p
 from typing import Optional
 
 import torch
@@ -668,3 +668,57 @@ def mel_loss(wave, fb, target=None, n_fft=1024, hop=256, clampv=1e-5, weight=1.0
     N.call("mv_mel_loss", _p(wave), _p(fb), _p(target), _p(mel), _p(acc), _p(gwave), B, T, n_fft, hop, n_mels,
            float(clampv), float(weight), int(kind), int(backward), _dt(wave), _stream())
     return acc, mel, gwave
+
+
+STFT_DEFAULT_RESOLUTIONS = ((512, 128), (1024, 256), (2048, 512))      # (n_fft, hop), Yamamoto et al. 2020 scaled to hop 256
+
+
+def stft_resolutions(resolutions, T=None):
+    """The resolutions as a tuple of (n_fft, hop) int pairs, checked against what mv_stft_loss supports (the header lists it); with
+    T also the two conditions that involve the length.  ValueError names the offending resolution."""
+    try:
+        res = tuple((int(n), int(h)) for n, h in resolutions)
+        if any((n, h) != tuple(r) for (n, h), r in zip(res, resolutions)):       # (2.5 is not silently 2)
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"stft_loss: resolutions must be a sequence of (n_fft, hop) integer pairs, got {resolutions!r}") from None
+    if not 1 <= len(res) <= 8:
+        raise ValueError(f"stft_loss: between 1 and 8 resolutions are supported, got {len(res)}")
+    for n, h in res:
+        if n < 32 or n > 2048 or n & (n - 1):
+            raise ValueError(f"stft_loss: resolution {(n, h)}: n_fft must be a power of two in [32, 2048]")
+        if h < 1 or h > n:
+            raise ValueError(f"stft_loss: resolution {(n, h)}: hop must lie in [1, n_fft]")
+        if (n - h) % 2:
+            raise ValueError(f"stft_loss: resolution {(n, h)}: n_fft - hop must be even")
+        if T is not None and T % h:
+            raise ValueError(f"stft_loss: resolution {(n, h)}: T = {T} is not a multiple of hop = {h}")
+        if T is not None and (n - h) // 2 >= T:
+            raise ValueError(f"stft_loss: resolution {(n, h)}: the reflect pad {(n - h) // 2} does not fit T = {T}")
+    return res
+
+
+def stft_loss(fake, real, resolutions=STFT_DEFAULT_RESOLUTIONS, floor=1e-7, weight=1.0, backward=False):
+    """Multi-resolution STFT loss (mv_stft_loss; the definition is in the header).  Returns (loss fp32 [1] = weight * mean over the
+    resolutions of (sc + mag), sums fp32 [R, 3] = {S_num, S_den, sum |log M_fake - log M_real|} per resolution, gwave fp32 [B,1,T] =
+    d loss / d fake or None).  `real` is a constant."""
+    # the C entry point receives one B and one T for both waves: a mismatch would be an out-of-bounds device read
+    if fake.dim() != 3 or fake.shape[1] != 1:
+        raise ValueError(f"stft_loss: fake must be [B, 1, T], got {tuple(fake.shape)}")
+    if real.shape != fake.shape or real.dtype != fake.dtype or real.device != fake.device:
+        raise ValueError(f"stft_loss: real and fake must share shape, dtype and device, got {tuple(real.shape)} {real.dtype} "
+                         f"{real.device} and {tuple(fake.shape)} {fake.dtype} {fake.device}")
+    B, _, T = fake.shape
+    res = stft_resolutions(resolutions, T)
+    if not floor > 0:
+        raise ValueError(f"stft_loss: floor must be positive, got {floor}")
+    _need_gpu(fake, real)
+    dt = _dt(fake)
+    fake, real = _c(fake), _c(real.detach())
+    sums = _f32(len(res), 3, device=fake.device)         # (zeroed by the entry point's own fill launch)
+    loss = _f32(1, device=fake.device)
+    gwave = _zeros(B, 1, T, device=fake.device, dtype=torch.float32) if backward else None
+    ints = c_int * len(res)
+    N.call("mv_stft_loss", _p(fake), _p(real), B, T, len(res), ints(*(n for n, _ in res)), ints(*(h for _, h in res)), float(floor),
+           float(weight), _p(sums), _p(loss), _p(gwave), int(backward), dt, _stream())
+    return loss, sums, gwave

@@ -19,6 +19,7 @@ Operators (schemas as registered; ``act``: 0 none, 1 LeakyReLU, 2 tanh, 3 SiLU; 
   avg_pool1d, mpd_fold, disc_conv_stack              discriminators.py:72-79,94,56-66,97-107
   disc_conv_stack_fm, disc_conv_stack_features       the stack with HiFi-GAN's hidden-map feature matching
   gan_loss, mel_loss, mel_spectrogram                complete_vocoder.py:89-184, conditioned_hifigan.py:262-265; DESIGN.md section 2
+  stft_loss                                          the multi-resolution STFT loss of generator training
   fused_adamw_, fused_adamw_dev_, fused_adamw_hp_, fused_adamw_clip_   conditioned_hifigan.py:219 (torch.optim.AdamW semantics): one
                                                      kernel, the per-step inputs by value or from device memory, clipped or not
   multi_gather_acc_, zero_, grad_norm                gradient_accumulation_steps / max_grad_norm of configs/*train_config.yaml
@@ -221,6 +222,9 @@ def _install():
               lambda x, y, kind, c, w: (x, y, kind, c, w), [0, 1, 2, 3, 4])
     _register("mel_loss", "(Tensor wave, Tensor target, Tensor fb, int n_fft, int hop, float clampv, float weight, int kind) -> Tensor",
               Fn._MelL1, lambda *a: a, list(range(8)))
+    # multi-resolution STFT loss (defined by this build): resolution r is (n_ffts[r], hops[r]); real is a constant
+    _register("stft_loss", "(Tensor fake, Tensor real, int[] n_ffts, int[] hops, float floor, float weight) -> Tensor",
+              Fn._StftLoss, lambda *a: a, list(range(6)))
     _forward_only("mel_spectrogram", "(Tensor wave, Tensor fb, int n_fft, int hop, float clampv) -> Tensor",
                   lambda wave, fb, n_fft, hop, clampv: ops.mel_loss(wave, fb, None, n_fft, hop, clampv, 1.0, backward=False, want_mel=True)[1])
 
@@ -386,6 +390,10 @@ def _install_fakes():
     @fake("mel_loss")
     def _(wave, target, fb, n_fft, hop, clampv, weight, kind):
         return wave.new_empty((), dtype=torch.float32)
+
+    @fake("stft_loss")
+    def _(fake, real, n_ffts, hops, floor, weight):
+        return fake.new_empty((), dtype=torch.float32)
 
     @fake("mel_spectrogram")
     def _(wave, fb, n_fft, hop, clampv):

@@ -360,6 +360,23 @@ int mv_mel_loss(const void* wave, const float* fb, const float* target, float* m
                 int B, int T, int n_fft, int hop, int n_mels, float clampv, float weight, int kind, int backward,
                 int dtype, void* stream);
 
+/* Multi-resolution STFT loss of fake against real, both [B][1][T] of `dtype`; defined by this build (after Yamamoto et al. 2020,
+ * DESIGN.md section 5b; the reference has no such term).  n_fft[], hop[]: HOST arrays of n_res entries.  Per resolution (N, hop), with
+ * mv_mel_loss's framing: reflect pad (N-hop)/2, frame f < T/hop starts at f*hop - pad, periodic Hann of length N, one-sided rFFT
+ * (k = 0..N/2), P = re^2 + im^2, M = sqrt(max(P, floor)).  Over all n = B * (N/2+1) * (T/hop) bins:
+ *   S_num = sum (M_real - M_fake)^2,  S_den = sum M_real^2,  sc = sqrt(S_num) / sqrt(S_den),  mag = (1/n) sum |log M_fake - log M_real|
+ *   sums (fp32 [n_res][3], zeroed here by a fill launch) = {S_num, S_den, sum |log M_fake - log M_real|} per resolution
+ *   loss[0] = weight * (1/n_res) * sum_r (sc_r + mag_r)                                  (written, not accumulated)
+ *   backward != 0: gwave (fp32 [B][T], zero on entry) += d loss[0] / d fake; real is a constant.  Per bin
+ *     g_M = (M_f - M_r) / (sqrt(S_num) sqrt(S_den)) [0 when S_num == 0] + sign(log M_f - log M_r) / (n M_f) [sign(0) = 0],
+ *     g_M = 0 where P_fake <= floor;  g_X = g_M X_f / M_f;  the frame gradient is the real part of the adjoint DFT over the
+ *     one-sided bins (no doubling), times the window, scattered with atomics.  The sums are read from device memory.
+ * All arithmetic fp32; two launches (three with backward) after the fill, every resolution in each.  fake == real bit for bit gives
+ * loss and gradient exactly 0.  Supported: N a power of two in [32, 2048], 1 <= hop <= N, N - hop even, T % hop == 0,
+ * (N-hop)/2 < T, 1 <= n_res <= 8, floor > 0; anything else returns MV_ERR_ARG before any launch. */
+int mv_stft_loss(const void* fake, const void* real, int B, int T, int n_res, const int* n_fft, const int* hop, float floor,
+                 float weight, float* sums, float* loss, float* gwave, int backward, int dtype, void* stream);
+
 /* AdamW on a flat fp32 parameter arena (torch.optim.AdamW semantics; conditioned_hifigan.py:219): grads are first
  * gathered into a flat fp32 buffer by mv_multi_gather (descs_dev: device array of {const void* src; long dst_off; long n;
  * int dtype; int pad}; src == NULL -> zeros), which is also the buffer RCCL all-reduces. grad_scale multiplies g (1/world). */

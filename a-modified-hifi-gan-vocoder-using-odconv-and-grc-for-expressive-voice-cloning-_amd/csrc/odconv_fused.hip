@@ -40,6 +40,20 @@ struct OdP {
   int out_pair;   // fp32 launch whose OUTPUT rows are written in the MRF chain's pair-row format (streaming kernel, 64 output channels)
 };
 
+// What a launcher decided, reported instead of launching (od_dispatch's dry run; mv_odconv_cl_plan hands it out as out[0..13]).
+enum { OD_FAM_CL = 0, OD_FAM_MT = 1, OD_FAM_SAMPLE = 2, OD_FAM_KLOOP = 3, OD_FAM_STREAM = 4 };
+struct OdPlan {
+  int family;     // OD_FAM_*
+  int S, MW, NB;  // samples per workgroup; M-tiles per wave (stream: MT, M-tiles per workgroup); 16-column blocks per tile (sample: NT)
+  int kb_cin;     // cl, kloop: the KB template parameter; mt, sample, stream: CIN
+  int ti16;       // an fp32 kernel that reads its input as fp16 (TI = f16 / XF16)
+  int cols, rows; // GEMM columns per tile, GEMM rows per workgroup
+  int lds;        // dynamic LDS bytes
+  int gx, gy, gz; // grid
+  int slots;      // pooled_out partial sums per sample and GEMM row
+  int walk;       // mt: TL, column tiles a workgroup walks; stream: tpw, 16-column tiles per wave; others 0
+};
+
 template <typename T> struct WLoad;   // this lane's 8 packed weights -> fp32
 template <> struct WLoad<bf16> {
   static constexpr int BYTES = 16;
@@ -955,16 +969,13 @@ __global__ __launch_bounds__(256, 2) void odconv_cl_mt_kernel(const TI* __restri
 
 template <typename T, int MW, int NB, int CIN, typename TI = T>
 static int od_mt_launch(const void* x, const void* wp, const void* bias, const float* alpha, const float* pooled_in, const void* att_w,
-                        const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream, int* slots_out) {
+                        const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream, OdPlan* plan) {
   constexpr int ES = Mma<T>::ES;
   const int nrows = NB * 16 + 1;
   const size_t xbytes = (size_t)nrows * lds_row_stride(ES == 4 ? 4 * CIN : CIN * ES, 2);
   const size_t obytes = (size_t)NB * 16 * (4 * MW * 16 * ES + 16);
   const size_t lds = sizeof(float) * (OD_MAXK + 4 * MW * 16) + (xbytes > obytes ? xbytes : obytes);
   if (lds > 80 * 1024) return MV_ERR_UNSUPPORTED;
-  auto kern = odconv_cl_mt_kernel<T, MW, NB, CIN, 4, TI>;
-  static size_t lds_set = 0;
-  if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
   const int ntl = cdiv(p.nq, NB * 16);
   const int gy = cdiv(p.M / 16, 4 * MW);
   // about two workgroups per CU: enough to overlap each other's barriers, few enough to amortise the per-workgroup weight mix
@@ -974,7 +985,14 @@ static int od_mt_launch(const void* x, const void* wp, const void* bias, const f
   if (TL > 16) TL = 16;
   dim3 grid(cdiv(ntl, TL), gy, p.B);
   if (grid.y > 65535 || grid.z > 65535) return MV_ERR_UNSUPPORTED;
-  if (slots_out) { *slots_out = (int)grid.x; return MV_OK; }
+  if (plan) {
+    *plan = OdPlan{OD_FAM_MT, 1, MW, NB, CIN, !std::is_same<TI, T>::value, NB * 16, 4 * MW * 16, (int)lds, (int)grid.x, (int)grid.y,
+                   (int)grid.z, (int)grid.x, TL};
+    return MV_OK;
+  }
+  auto kern = odconv_cl_mt_kernel<T, MW, NB, CIN, 4, TI>;
+  static size_t lds_set = 0;
+  if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const TI*)x, (const T*)wp, (const T*)bias, alpha,
                      pooled_in, (const T*)att_w, (const T*)att_b, (T*)y, pooled_out, p, TL);
   return MV_OK;
@@ -1125,18 +1143,21 @@ __global__ __launch_bounds__(512) void odconv_sample_kernel(const T* __restrict_
 
 template <typename T, int CIN, int NT>
 static int od_sample_launch(const void* x, const void* wp, const void* bias, const float* alpha, const float* pooled_in, const void* att_w,
-                            const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream, int* slots_out) {
+                            const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream, OdPlan* plan) {
   if (!p.transposed || p.ntaps != 2 || p.K > 4 || p.Cin != CIN || p.M % 128 || p.nq > NT * 16 || p.nq <= (NT - 1) * 16 ||
       p.shift_lo != -1 || p.act > ACT_LRELU || (long)p.Tin * CIN * 2 > 0x7fff0000L)
     return MV_ERR_UNSUPPORTED;
   const size_t lds = sizeof(float) * (OD_MAXK + (CIN > 256 ? CIN : 256)) + (size_t)(p.nq + 1) * lds_row_stride(CIN * 2, 2);
   if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
+  dim3 grid(p.M / 128, p.B);
+  if (grid.y > 65535) return MV_ERR_UNSUPPORTED;
+  if (plan) {
+    *plan = OdPlan{OD_FAM_SAMPLE, 1, 1, NT, CIN, 0, NT * 16, 128, (int)lds, (int)grid.x, (int)grid.y, 1, 1, 0};
+    return MV_OK;
+  }
   auto kern = odconv_sample_kernel<T, CIN, NT>;
   static size_t lds_set = 0;
   if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }
-  dim3 grid(p.M / 128, p.B);
-  if (grid.y > 65535) return MV_ERR_UNSUPPORTED;
-  if (slots_out) { *slots_out = 1; return MV_OK; }
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, (const T*)x, (const T*)wp, (const T*)bias, alpha, pooled_in,
                      (const T*)att_w, (const T*)att_b, (T*)y, pooled_out, p);
   return MV_OK;
@@ -1475,7 +1496,7 @@ __global__ __launch_bounds__(256) void odconv_kloop_kernel(const T* __restrict__
 template <typename T, int S, int NB, int MW>
 static int od_kloop_launch(const void* x, const void* wp, const void* bias, const float* alpha, const float* pooled_in,
                            const void* att_w, const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream,
-                           int* slots_out) {
+                           OdPlan* plan) {
   using M = Mma<T>;
   constexpr int PD = M::ES == 4 ? 4 : 8;
   if (p.nq > NB * 16 || p.K > 4 || p.Cin % 32 || (p.Cin / 32) % PD || p.ksteps % PD || p.nchunks != 4 * p.ksteps || p.ntaps > 2)
@@ -1486,15 +1507,18 @@ static int od_kloop_launch(const void* x, const void* wp, const void* bias, cons
   const size_t obytes = (size_t)S * NB * 16 * (64 * MW * M::ES + 16);
   const size_t lds = sizeof(float) * (S * OD_MAXK + S * (p.Cin > 256 ? p.Cin : 256)) + (xbytes > obytes ? xbytes : obytes);
   if (lds > 160 * 1024 || (long)p.B * p.Tin * p.Cin * M::ES > 0x7fff0000L) return MV_ERR_UNSUPPORTED;
+  dim3 grid(cdiv(p.M / 16, 4 * MW), cdiv(p.B, S));
+  if (grid.y > 65535) return MV_ERR_UNSUPPORTED;
+  if (plan) {
+    *plan = OdPlan{OD_FAM_KLOOP, S, MW, NB, 4, 0, NB * 16, 4 * MW * 16, (int)lds, (int)grid.x, (int)grid.y, 1, 1, 0};
+    return MV_OK;
+  }
   auto kern = odconv_kloop_kernel<T, S, NB, 4, MW>;
   static size_t lds_set = 0;
   if (lds > lds_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_set = lds;
   }
-  dim3 grid(cdiv(p.M / 16, 4 * MW), cdiv(p.B, S));
-  if (grid.y > 65535) return MV_ERR_UNSUPPORTED;
-  if (slots_out) { *slots_out = 1; return MV_OK; }
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)x, (const T*)wp, (const T*)bias, alpha, pooled_in,
                      (const T*)att_w, (const T*)att_b, (T*)y, pooled_out, p);
   return MV_OK;
@@ -1503,22 +1527,25 @@ static int od_kloop_launch(const void* x, const void* wp, const void* bias, cons
 template <typename T, int S, int MW, int NB, int KB>
 static int od_launch(const void* x, const void* wp, const void* bias, const float* alpha, const float* pooled_in,
                      const void* att_w, const void* att_b, const void* film, void* y, float* pooled_out, OdP p,
-                     hipStream_t stream, int* slots_out) {
+                     hipStream_t stream, OdPlan* plan) {
   using M = Mma<T>;
   p.nrows = NB * 16 + (p.ntaps - 1) * (p.transposed ? 1 : p.dil);
   const size_t xbytes = (size_t)S * p.nrows * lds_row_stride(M::ES == 4 ? 4 * p.Cin : p.Cin * M::ES, 2);
   const size_t obytes = (size_t)S * NB * 16 * (4 * MW * 16 * M::ES + 16);    // staged output tile reuses the x region
   const size_t lds = sizeof(float) * (S * OD_MAXK + S * 4 * MW * 16) + (xbytes > obytes ? xbytes : obytes);
   if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
+  dim3 grid(cdiv(p.nq, NB * 16), cdiv(p.M / 16, 4 * MW), cdiv(p.B, S));
+  if (grid.y > 65535 || grid.z > 65535) return MV_ERR_UNSUPPORTED;
+  if (plan) {
+    *plan = OdPlan{OD_FAM_CL, S, MW, NB, KB, 0, NB * 16, 4 * MW * 16, (int)lds, (int)grid.x, (int)grid.y, (int)grid.z, (int)grid.x, 0};
+    return MV_OK;
+  }
   auto kern = odconv_cl_kernel<T, S, MW, NB, (M::ES == 2 || MW * NB <= 3), KB>;   // fp32: prefetch only in the small (input_proj) instantiation
   static size_t lds_set = 0;
   if (lds > lds_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_set = lds;
   }
-  dim3 grid(cdiv(p.nq, NB * 16), cdiv(p.M / 16, 4 * MW), cdiv(p.B, S));
-  if (grid.y > 65535 || grid.z > 65535) return MV_ERR_UNSUPPORTED;
-  if (slots_out) { *slots_out = (int)grid.x; return MV_OK; }
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)x, (const T*)wp, (const T*)bias, alpha, pooled_in,
                      (const T*)att_w, (const T*)att_b, (const T*)film, (T*)y, pooled_out, p);
   return MV_OK;
@@ -1885,7 +1912,7 @@ __global__ __launch_bounds__(OS_NW * 64) void odconv_stream_kernel(const void* _
 
 template <int CIN, int MT, bool XF16>
 static int od_stream_launch(const void* x, const void* wp, const void* bias, const float* alpha, const float* pooled_in, const void* att_w,
-                            const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream, int* slots_out) {
+                            const void* att_b, void* y, float* pooled_out, OdP p, hipStream_t stream, OdPlan* plan) {
   constexpr int KST = 2 * CIN / 32;
   if ((long)p.Tin * OS_RB >= (1l << 31) || (long)p.Tout * p.Cout * 4 >= (1l << 31) || p.Cout % 16 || p.K > 4) return MV_ERR_UNSUPPORTED;
   const size_t lds = (size_t)MT * KST * 2048 + sizeof(float) * (OD_MAXK + MT * 16 + OS_NW * MT * 16) + (size_t)OS_NW * OS_RING;
@@ -1897,8 +1924,11 @@ static int od_stream_launch(const void* x, const void* wp, const void* bias, con
   int tpw = cdiv(tiles, wgs * OS_NW);
   if (tpw < 1) tpw = 1;
   const int gx = cdiv(tiles, tpw * OS_NW);
-  if (slots_out) { *slots_out = gx; return MV_OK; }
   if (gy > 65535 || p.B > 65535) return MV_ERR_UNSUPPORTED;
+  if (plan) {
+    *plan = OdPlan{OD_FAM_STREAM, 1, MT, 1, CIN, XF16, 16, MT * 16, (int)lds, gx, gy, p.B, gx, tpw};
+    return MV_OK;
+  }
   auto kern = odconv_stream_kernel<CIN, MT, XF16>;
   static bool set = false;
   if (!set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
@@ -1907,19 +1937,20 @@ static int od_stream_launch(const void* x, const void* wp, const void* bias, con
   return MV_OK;
 }
 
-// Picks the kernel variant for a layer and launches it - or, with slots_out, only reports how many partial-sum slots per sample
-// that launch writes to pooled_out (the variant sets the grid, so the caller sizes pooled_out from the same decision).
+// Picks the kernel variant for a layer and launches it - or, with `plan`, only reports what that launch would be (no HIP call): the
+// instantiation, its tile, LDS and grid, and how many partial-sum slots per sample it writes to pooled_out (the variant sets the
+// grid, so the caller sizes pooled_out from the same decision).
 static int od_dispatch(const void* x, const void* packed, const void* bias, const float* alpha, const float* pooled_in,
                        const void* att_w, const void* att_b, const void* film_proj, void* y, float* pooled_out, OdP p,
-                       int dtype, hipStream_t st_, int* slots_out) {
+                       int dtype, hipStream_t st_, OdPlan* plan) {
   const int K = p.K, B = p.B, Cin = p.Cin, transposed = p.transposed, act = p.act;
   const int ntiles = cdiv(p.nq, 16);
   const long wbytes = (long)K * p.M * p.ksteps * 32 * (dtype == MV_F32 ? 4 : 2);
   int rc = MV_ERR_DTYPE;
   // with the unconditional (clamped) prefetch the prefetching instantiation wins for the short-K upsamplers as well (ups3 48 -> 44 us)
 #define OD_GO(S_, MW_, NB_) do { \
-    if (K <= 4) rc = od_launch<T, S_, MW_, NB_, 4>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); \
-    else rc = od_launch<T, S_, MW_, NB_, 8>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, slots_out); } while (0)
+    if (K <= 4) rc = od_launch<T, S_, MW_, NB_, 4>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, plan); \
+    else rc = od_launch<T, S_, MW_, NB_, 8>(x, packed, bias, alpha, pooled_in, att_w, att_b, film_proj, y, pooled_out, p, st_, plan); } while (0)
   if (p.in_f16 && (dtype != MV_F32 || ntiles <= 3 || wbytes > (1 << 20))) return MV_ERR_UNSUPPORTED;   // (only the multi-tile kernel below)
   if (p.out_pair && (dtype != MV_F32 || ntiles <= 3 || wbytes > (1 << 20) || p.Cout != 64 || p.in_f16)) return MV_ERR_UNSUPPORTED;   // (only the 64-channel streaming kernel)
   MV_DISPATCH(dtype, {
@@ -1931,11 +1962,11 @@ static int od_dispatch(const void* x, const void* packed, const void* bias, cons
         // operands, 3 MFMAs per product) 97 us with two M-tiles per wave vs 133 with one.  The launch is bound by the weight
         // stream out of L2 (16 sample groups x 16.8 MB = 268 MB), not by the matrix pipe (12 us) - see DESIGN.md
         if constexpr (sizeof(T) == 4) {   // (four samples per workgroup halve the L2 stream but leave one wave per SIMD: 58.6 us)
-          rc = od_kloop_launch<T, 2, 3, 2>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-          if (rc == MV_ERR_UNSUPPORTED) rc = od_kloop_launch<T, 1, 3, 2>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+          rc = od_kloop_launch<T, 2, 3, 2>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+          if (rc == MV_ERR_UNSUPPORTED) rc = od_kloop_launch<T, 1, 3, 2>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
         } else {
-          rc = od_kloop_launch<T, 2, 3, 1>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-          if (rc == MV_ERR_UNSUPPORTED) rc = od_kloop_launch<T, 1, 3, 1>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+          rc = od_kloop_launch<T, 2, 3, 1>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+          if (rc == MV_ERR_UNSUPPORTED) rc = od_kloop_launch<T, 1, 3, 1>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
         }
       }
       // two samples per workgroup share the staged weights, but a grid that leaves CUs idle loses more: input_proj at B = 32 is
@@ -1950,11 +1981,11 @@ static int od_dispatch(const void* x, const void* packed, const void* bias, cons
       // of once per tile (37 -> 28.5 us; 144-column tiles without the x look-ahead measured 34 us)
       // the whole sample resident in LDS, the mixed fragments streamed (ups1 at B = 32: see odconv_sample_kernel)
       if (transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && Cin == 256 && B * (p.M / 128) >= 128) {
-        if constexpr (sizeof(T) == 2) rc = od_sample_launch<T, 256, 17>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+        if constexpr (sizeof(T) == 2) rc = od_sample_launch<T, 256, 17>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
       }
       if (rc == MV_ERR_UNSUPPORTED && transposed && p.ntaps == 2 && K <= 4 && !film_proj && act <= ACT_LRELU && Cin == 256) {
         // (fp32: 16 resident fragment PAIRS per wave need 256 VGPRs = one wave per SIMD: 98 us vs 77 on the one-tile kernel - not used)
-        if constexpr (sizeof(T) == 2) rc = od_mt_launch<T, 1, 6, 256>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+        if constexpr (sizeof(T) == 2) rc = od_mt_launch<T, 1, 6, 256>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
       }
       if (rc == MV_ERR_UNSUPPORTED) OD_GO(1, 2, 9);      // (fp32: 64- / 96-column tiles measured 96 / 94 us vs 76)
       if (rc == MV_ERR_UNSUPPORTED) OD_GO(1, 1, 3);
@@ -1964,20 +1995,20 @@ static int od_dispatch(const void* x, const void* packed, const void* bias, cons
         // 128-column tiles for 64 input channels; 64-column tiles for 128 (8 resident A fragments per M-tile: the wider tile
         // would need > 256 VGPRs, i.e. one wave per SIMD - measured 42 vs 24.5 us)
         if constexpr (sizeof(T) == 2) {
-          if (Cin == 64) rc = od_mt_launch<T, 2, 8, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-          else rc = od_mt_launch<T, 2, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+          if (Cin == 64) rc = od_mt_launch<T, 2, 8, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+          else rc = od_mt_launch<T, 2, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
         } else {   // fp32 (operands are hi/lo register pairs): 64-column tiles; at 128 channels ONE M-tile per wave (two cost a wave per SIMD: 60 us)
           if (act <= ACT_LRELU) {    // streaming form: 256-byte input rows (64 fp32 / 128 fp16 channels)
-            if (p.in_f16 && Cin == 128) rc = od_stream_launch<128, 4, true>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-            else if (!p.in_f16 && Cin == 64) rc = od_stream_launch<64, 8, false>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
+            if (p.in_f16 && Cin == 128) rc = od_stream_launch<128, 4, true>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+            else if (!p.in_f16 && Cin == 64) rc = od_stream_launch<64, 8, false>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
           }
           if (rc != MV_ERR_UNSUPPORTED) { /* launched (or sized) */ }
           else if (p.out_pair) return rc;
           else if (p.in_f16) {
-            if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-            else rc = od_mt_launch<T, 1, 4, 128, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-          } else if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);
-          else rc = od_mt_launch<T, 1, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, slots_out);   // ups2 49 -> 38 us
+            if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+            else rc = od_mt_launch<T, 1, 4, 128, f16>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+          } else if (Cin == 64) rc = od_mt_launch<T, 2, 4, 64>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);
+          else rc = od_mt_launch<T, 1, 4, 128>(x, packed, bias, alpha, pooled_in, att_w, att_b, y, pooled_out, p, st_, plan);   // ups2 49 -> 38 us
         }
       }
       if (p.in_f16 || p.out_pair) return rc;                 // only the multi-tile / streaming kernels widen their input / write pair rows
@@ -2040,16 +2071,39 @@ extern "C" size_t mv_odconv_cl_pool_floats(int B, int Cin, int Tin, int Cout, in
   return mv_odconv_cl_pool_floats_in(B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, transposed, K, act, has_film, dtype, 0);
 }
 
-extern "C" size_t mv_odconv_cl_pool_floats_in(int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil,
-                                            int transposed, int K, int act, int has_film, int dtype, int in_f16) {
+// the dry run of od_dispatch for a geometry: the launch's return code for valid pointers, and for MV_OK the plan
+static int od_plan(OdPlan* plan, int* M, int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil, int transposed,
+                   int K, int act, int has_film, int dtype, int in_f16, int out_pair) {
   OdP p;
-  if (!od_make(&p, B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, transposed, K, act, 0.1f, has_film ? 8 : 0)) return 0;
-  p.in_f16 = (in_f16 && dtype == MV_F32) ? 1 : 0;
-  int slots = 0;
+  if (!od_make(&p, B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, transposed, K, act, 0.1f, has_film ? 8 : 0)) return MV_ERR_UNSUPPORTED;
+  p.in_f16 = in_f16;
+  p.out_pair = out_pair;
+  *M = p.M;
   static const int dummy = 0;   // non-null stand-ins: the dry run launches nothing and touches no memory
   const void* d = &dummy;
-  const int rc = od_dispatch(d, d, nullptr, nullptr, nullptr, nullptr, nullptr, has_film ? d : nullptr, nullptr, nullptr, p,
-                             dtype, nullptr, &slots);
-  if (rc != MV_OK || slots <= 0) return 0;
-  return (size_t)slots * p.M;
+  return od_dispatch(d, d, nullptr, nullptr, nullptr, nullptr, nullptr, has_film ? d : nullptr, nullptr, nullptr, p, dtype, nullptr, plan);
+}
+
+extern "C" size_t mv_odconv_cl_pool_floats_in(int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil,
+                                            int transposed, int K, int act, int has_film, int dtype, int in_f16) {
+  OdPlan plan = {};
+  int M = 0;
+  const int rc = od_plan(&plan, &M, B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, transposed, K, act, has_film, dtype,
+                         (in_f16 && dtype == MV_F32) ? 1 : 0, 0);
+  if (rc != MV_OK || plan.slots <= 0) return 0;
+  return (size_t)plan.slots * M;
+}
+
+extern "C" int mv_odconv_cl_plan(int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil, int transposed, int K,
+                                 int act, int has_film, int dtype, int in_f16, int out_pair, int* out) {
+  MV_CHECK_ARG(out);
+  OdPlan plan = {};
+  int M = 0;
+  const int rc = od_plan(&plan, &M, B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, transposed, K, act, has_film, dtype, in_f16 ? 1 : 0,
+                         out_pair ? 1 : 0);
+  if (rc != MV_OK) return rc;
+  const int v[14] = {plan.family, plan.S, plan.MW, plan.NB, plan.kb_cin, plan.ti16, plan.cols, plan.rows, plan.lds, plan.gx, plan.gy,
+                     plan.gz, plan.slots, plan.walk};
+  for (int i = 0; i < 14; ++i) out[i] = v[i];
+  return MV_OK;
 }

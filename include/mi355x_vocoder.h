@@ -245,6 +245,19 @@ size_t mv_odconv_cl_pool_floats(int B, int Cin, int Tin, int Cout, int Tout, int
 /* the same for a launch through mv_odconv_cl_fwd_in16 (in_f16 != 0, dtype MV_F32): the input-widening variants set their own grids */
 size_t mv_odconv_cl_pool_floats_in(int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil,
                                    int transposed, int K, int act, int has_film, int dtype, int in_f16);
+/* What the dispatcher of the three entry points above would do, asked without a GPU (no HIP call): the return code of the launch for
+ * this geometry with valid, aligned pointers - mv_odconv_cl_fwd (in_f16 = out_pair = 0; has_film: a film_proj is passed),
+ * mv_odconv_cl_fwd_in16 (in_f16 = 1, dtype MV_F32) or mv_odconv_cl_fwd_pair (out_pair = 1, dtype MV_F32) - and for MV_OK the plan in
+ * out[0..13]:
+ *   [0] kernel family: 0 odconv_cl_kernel<T,S,MW,NB,PF,KB>, 1 odconv_cl_mt_kernel<T,MW,NB,CIN,4,TI>, 2 odconv_sample_kernel<T,CIN,NT>,
+ *       3 odconv_kloop_kernel<T,S,NB,KB,MW>, 4 odconv_stream_kernel<CIN,MT,XF16>;
+ *   [1] S, [2] MW (stream: MT), [3] NB (sample: NT; stream: 1), [4] KB (cl, kloop) or CIN (mt, sample, stream), [5] 1 if an fp32
+ *       kernel reads fp16 input (TI = f16, XF16);
+ *   [6] GEMM columns per tile, [7] GEMM rows per workgroup, [8] dynamic LDS bytes, [9..11] grid x, y, z;
+ *   [12] pooled_out slots per sample (mv_odconv_cl_pool_floats = slots x GEMM rows);
+ *   [13] mt: TL, the column tiles one workgroup walks; stream: 16-column tiles per wave; otherwise 0. */
+int mv_odconv_cl_plan(int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil, int transposed, int K,
+                      int act, int has_film, int dtype, int in_f16, int out_pair, int* out);
 /* Generator prologue in one launch: input_proj's attention alpha fp32 [B][K] (odconv.py:36-40) and mel [B][C][T] -> x_cl [B][T][C]
  * (one workgroup per sample), the FiLM projection film_proj [B][F2] = W cond + b with cond = cat(spk [B][ds], emo [B][de])
  * truncated / zero-padded to cond_dim (grc_lora.py:82-105; film_proj NULL = no conditioning; extra workgroups of the same grid,

@@ -211,3 +211,29 @@ def sharpen_attention(sd, factor=20.0):
         if k.endswith("kernel_attention.1.weight"):
             out[k] = sd[k] * factor
     return out
+
+
+# ------------------------------------------------------------------------------------------------ split-operand products
+def bf16_split(t):
+    """csrc/mfma.h Mma<float>::split: hi = bf16(v), lo = bf16(v - hi), both round-to-nearest; returned as float64."""
+    hi = t.float().bfloat16().double()
+    lo = (t.double() - hi).float().bfloat16().double()
+    return hi, lo
+
+
+def f16_split(t):
+    """The streaming kernels' pieces: hi = f16(v), lo = f16(v - hi), round-to-nearest, f16 subnormals kept; as float64."""
+    hi = t.float().half().double()
+    lo = (t.double() - hi).float().half().double()
+    return hi, lo
+
+
+def split_product(bilinear, w, x, drop=(), split=None):
+    """The fp32 storage mode's product of two split operands under a bilinear map (a convolution, a GEMM), in float64:
+    bilinear(wh, xh) + bilinear(wh, xl) + bilinear(wl, xh); the lo * lo term is never formed.  `drop` names terms a faulty kernel
+    loses ("hl": weight hi x activation lo, "lh": weight lo x activation hi); `split` = f16_split for the streaming kernels."""
+    split = split or bf16_split
+    wh, wl = split(w)
+    xh, xl = split(x)
+    terms = {"hh": (wh, xh), "hl": (wh, xl), "lh": (wl, xh)}
+    return sum(bilinear(a, b) for k, (a, b) in terms.items() if k not in drop)

@@ -177,13 +177,32 @@ inline MrfChainWs mrf_chain_ws(int B, int T_, int dtype) {
 }
 // conv_out.hip: the chain's fused ending, y = act(conv(a f + b + x)).  `ab` is read unless tail.part8 is set, which only the form
 // that mvi_conv_out_affine_takes_partials announces accepts; that form alone reads row forms other than MRF_ROWS_FP32.
+// What the launchers of an MRF entry decided, reported instead of launching (the dry run behind mv_mrf_plan, which hands it out as
+// out[0..19] in this order).  Every launcher below takes a trailing `MrfPlan* plan`: null launches; non-null fills the plan (and *tail)
+// and returns before the first HIP call, so the geometry a launch uses and the geometry the query reports are the same lines of code.
+struct MrfPlan {
+  int form;                  // 0 tile form (mrf_kernel), 1 streaming form (mrf_stream_kernel)
+  int nwaves, ntw;           // waves per workgroup; 16-step column tiles per wave and iteration (streaming: 1)
+  int std_mask;              // bit i: block i runs the STD = true instantiation (dilations (1, 3, 5))
+  int nwg, nit, wide;        // workgroups per sample; tile form: tiles a workgroup walks, and whether the fp32 chain's first pass is wide
+  int tpw, L;                // streaming form: column tiles and time steps of a wave's span
+  int lds, lds_wide;         // dynamic LDS bytes of the passes (streaming: of F0 / F); of the wide pass
+  int lds_stat;              // streaming form: of the passes that stage the branch convs only (V0, A)
+  int gx, gy;                // grid of the passes
+  int kind;                  // MrfChainKind; -1: block entry
+  int out_family;            // output conv: -1 none, 0 conv_out_affine_kernel<T, 64>, 1 conv_out_affine_mfma_kernel<64, row form>
+  int row_form;              // MrfRowForm the output conv reads x in; -1 none
+  int launches;              // kernel launches of the whole call
+  int hmax;                  // largest halo of the call's blocks
+  int out_lds;               // dynamic LDS bytes of the output conv
+};
 bool mvi_conv_out_affine_takes_partials(int dtype, int ks);
 int mvi_conv_out_affine(const MrfChainTail& tail, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
-                        int pad, int act, int dtype, float eps, hipStream_t stream);
+                        int pad, int act, int dtype, float eps, hipStream_t stream, MrfPlan* plan = nullptr);
 // mrf_stream.hip: the chain in its streaming form (MV_F32_W16, dilations (1, 3, 5) only).  out non-null: the last block's output is
 // written as fp32 rows; otherwise *tail is filled.  x_pair_in: x arrives as pair rows.
 int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, int nblocks, char* ws, const MrfChainWs& lay, int B, int Tn,
-                         float eps, hipStream_t stream, bool x_pair_in, MrfChainTail* tail);
+                         float eps, hipStream_t stream, bool x_pair_in, MrfChainTail* tail, MrfPlan* plan = nullptr);
 
 // Zero fill as a KERNEL launch.  hipMemsetAsync becomes a memset node when a stream is being captured, and on this ROCm build a memset
 // node is not reliably ordered in front of the kernel node that follows it in a replayed graph: a captured training step whose

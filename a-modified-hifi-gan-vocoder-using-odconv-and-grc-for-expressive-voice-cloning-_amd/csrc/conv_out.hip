@@ -380,7 +380,7 @@ bool mvi_conv_out_affine_takes_partials(int dtype, int ks) {
 }
 
 int mvi_conv_out_affine(const MrfChainTail& tail, const float* ab, const float* wt, float bias, void* y, int B, int T_, int C, int ks,
-                        int pad, int act, int dtype, float eps, hipStream_t stream) {
+                        int pad, int act, int dtype, float eps, hipStream_t stream, MrfPlan* plan) {
   if (C != 64 || 2 * pad != ks - 1) return MV_ERR_UNSUPPORTED;
   const bool partials = mvi_conv_out_affine_takes_partials(dtype, ks);
   if ((tail.form != MRF_ROWS_FP32 || tail.part8) && !partials) return MV_ERR_UNSUPPORTED;
@@ -396,6 +396,7 @@ int mvi_conv_out_affine(const MrfChainTail& tail, const float* ab, const float* 
       case MRF_ROWS_HL8: kern = conv_out_affine_mfma_kernel<64, MRF_ROWS_HL8>; slot = 2; break;
       default: return MV_ERR_ARG;
     }
+    if (plan) { plan->out_family = 1; plan->row_form = tail.form; plan->out_lds = (int)lds; plan->launches += 1; return MV_OK; }
     static size_t lds_set_m[3] = {0, 0, 0};
     if (lds > lds_set_m[slot]) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -408,6 +409,7 @@ int mvi_conv_out_affine(const MrfChainTail& tail, const float* ab, const float* 
   MV_DISPATCH(dtype, {
     const size_t lds = (size_t)(256 + ks - 1) * (64 * Mma<T>::ES + 16);
     if (lds > 160 * 1024) return MV_ERR_UNSUPPORTED;
+    if (plan) { plan->out_family = 0; plan->row_form = tail.form; plan->out_lds = (int)lds; plan->launches += 1; return MV_OK; }
     auto kern = conv_out_affine_kernel<T, 64>;
     static size_t lds_set = 0;
     if (lds > lds_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; }

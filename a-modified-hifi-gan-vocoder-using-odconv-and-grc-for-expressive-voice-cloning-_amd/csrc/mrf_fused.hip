@@ -587,8 +587,11 @@ __global__ __launch_bounds__(NWAVES * 64) void mrf_kernel(const StT<T>* __restri
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
+            // explicit fmas: left to the compiler's contraction, the masked and the maskless instantiation of this lambda fused
+            // different elements (fp32: v_mul + v_pk_add for half of them without a mask, v_fmac for all with one), so a mask of
+            // ones did not reproduce the maskless call bit for bit (tests/test_gpu_mrf_arms.py)
             const float sc = rs * ga[r];
-            float w = f[m][n][r] * sc + (be[r] - mu * sc);
+            float w = __builtin_fmaf(f[m][n][r], sc, __builtin_fmaf(-mu, sc, be[r]));
             if (HAS_MASK) w = (t < Tn && mask[((size_t)b * Tn + t) * MRF_C + 16 * m + 4 * g + r]) ? w * mask_scale : 0.f;
             o[r] = w + xr[r];
           }
@@ -675,22 +678,50 @@ static inline void mrf_geometry(int B, int Tn, int tile_t, int* nwg, int* nit) {
   *nwg = cdiv(ntiles, it);
 }
 
+// The geometry of the tile form for one instantiation <T, NWAVES, NTW>, for the block entry (nblocks = 1, chain false) and the chain:
+// workgroups and iterations, dynamic LDS, the chain's wide first pass, the grid.  mrf_launch and mrf_chain_launch launch what this
+// returns and mv_mrf_plan reports it; MV_ERR_UNSUPPORTED where the shared tile does not fit 160 KB or a halo exceeds MRF_HMAX.
 template <typename T, int NWAVES, int NTW>
-static int mrf_launch(const void* x, void* out, const void* packed, const MrfMeta& meta, float* ws,
-                      const uint8_t* mask, float mask_scale, int B, int Tn, float eps, hipStream_t stream) {
+static int mrf_tile_plan(const MrfMeta* metas, int nblocks, bool chain, int B, int Tn, MrfPlan* p) {
   using M = Mma<T>;
   constexpr int FS = M::NSETS * FRAG_BYTES;
   constexpr int RS = (M::ES == 4 ? 2 * MRF_C * 2 : MRF_C * M::ES) + 32;   // as in the kernel
-  int nwg, nit;
+  int nwg, nit, hmax = 0, stdm = 0;
   mrf_geometry(B, Tn, NWAVES * NTW * 16, &nwg, &nit);
-  const size_t tile_rows = M::ES == 4 ? (size_t)NWAVES * NTW * 16 + 2 * meta.halo : (size_t)NWAVES * (NTW * 16 + 2 * meta.halo);
+  for (int i = 0; i < nblocks; ++i) {
+    hmax = metas[i].halo > hmax ? metas[i].halo : hmax;
+    if (mrf_meta_is_std(metas[i])) stdm |= 1 << i;
+  }
+  const size_t tile_rows = M::ES == 4 ? (size_t)NWAVES * NTW * 16 + 2 * hmax : (size_t)NWAVES * (NTW * 16 + 2 * hmax);
   const size_t lds = (size_t)(MRF_CONV_FRAGS + MRF_RES_FRAGS + MRF_FUS_FRAGS) * FS + MRF_TAB_FLOATS * 4 + (32 + 16) * 4 +
                      (size_t)NWAVES * 32 * 4 + tile_rows * RS;
-  if (lds > 160 * 1024 || meta.halo > MRF_HMAX) return MV_ERR_UNSUPPORTED;
+  if (lds > 160 * 1024 || hmax > MRF_HMAX) return MV_ERR_UNSUPPORTED;
+  // fp32 chain: the statistics-of-v pass of block 0 keeps only the branch-conv fragments in LDS and runs 32-step wave tiles (see the
+  // kernel); same workgroup count, half the iterations, so the partial-sum buffers line up with the 16-step passes
+  constexpr bool WIDE_OK = (M::ES == 4) && NTW == 1;
+  const size_t lds_wide = (size_t)MRF_CONV_FRAGS * FS + MRF_TAB_FLOATS * 4 + (32 + 16) * 4 + (size_t)NWAVES * 32 * 4 +
+                          ((size_t)NWAVES * 2 * 16 + 2 * hmax) * RS;
+  const bool wide = chain && WIDE_OK && nit >= 2 && nit % 2 == 0 && lds_wide <= 160 * 1024 && Tn % (NWAVES * 32) == 0;
+  *p = MrfPlan{};
+  p->form = 0; p->nwaves = NWAVES; p->ntw = NTW; p->std_mask = stdm; p->nwg = nwg; p->nit = nit; p->wide = wide;
+  p->lds = (int)lds; p->lds_wide = wide ? (int)lds_wide : 0; p->gx = nwg; p->gy = B; p->hmax = hmax;
+  p->kind = -1; p->out_family = -1; p->row_form = -1;
+  return MV_OK;
+}
+
+template <typename T, int NWAVES, int NTW>
+static int mrf_launch(const void* x, void* out, const void* packed, const MrfMeta& meta, float* ws,
+                      const uint8_t* mask, float mask_scale, int B, int Tn, float eps, hipStream_t stream, MrfPlan* plan) {
+  MrfPlan g;
+  const int prc = mrf_tile_plan<T, NWAVES, NTW>(&meta, 1, false, B, Tn, &g);
+  if (prc != MV_OK) return prc;
+  if (plan) { g.launches = 3; *plan = g; return MV_OK; }
+  const int nwg = g.nwg, nit = g.nit;
+  const size_t lds = (size_t)g.lds;
   float* part5 = ws;
   float* part8 = ws + (size_t)B * nwg * 32;
-  dim3 grid(nwg, B), block(NWAVES * 64);
-  const bool stdm = mrf_meta_is_std(meta);
+  dim3 grid(g.gx, g.gy), block(NWAVES * 64);
+  const bool stdm = g.std_mask & 1;
   auto k1 = stdm ? mrf_kernel<T, NWAVES, NTW, 1, true> : mrf_kernel<T, NWAVES, NTW, 1, false>;
   auto k2 = stdm ? mrf_kernel<T, NWAVES, NTW, 2, true> : mrf_kernel<T, NWAVES, NTW, 2, false>;
   auto k3 = stdm ? mrf_kernel<T, NWAVES, NTW, 3, true> : mrf_kernel<T, NWAVES, NTW, 3, false>;
@@ -759,7 +790,7 @@ enum MrfChainKind {
 };
 
 template <typename T, int NWAVES, int NTW>
-static int mrf_chain_launch(const MrfChainReq& r, const MrfChainWs& lay, MrfChainKind kind, MrfChainTail* tail) {
+static int mrf_chain_launch(const MrfChainReq& r, const MrfChainWs& lay, MrfChainKind kind, MrfChainTail* tail, MrfPlan* plan) {
   const void* const* packed = r.packed;
   const MrfMeta* metas = r.metas;
   char* const ws = r.ws;
@@ -768,29 +799,31 @@ static int mrf_chain_launch(const MrfChainReq& r, const MrfChainWs& lay, MrfChai
   const hipStream_t stream = r.stream;
   using M = Mma<T>;
   constexpr int FS = M::NSETS * FRAG_BYTES;
-  constexpr int RS = (M::ES == 4 ? 2 * MRF_C * 2 : MRF_C * M::ES) + 32;   // as in the kernel
-  int nwg, nit, hmax = 0;
-  mrf_geometry(B, Tn, NWAVES * NTW * 16, &nwg, &nit);
-  for (int i = 0; i < nblocks; ++i) hmax = metas[i].halo > hmax ? metas[i].halo : hmax;
-  const size_t tile_rows = M::ES == 4 ? (size_t)NWAVES * NTW * 16 + 2 * hmax : (size_t)NWAVES * (NTW * 16 + 2 * hmax);
-  const size_t lds = (size_t)(MRF_CONV_FRAGS + MRF_RES_FRAGS + MRF_FUS_FRAGS) * FS + MRF_TAB_FLOATS * 4 + (32 + 16) * 4 +
-                     (size_t)NWAVES * 32 * 4 + tile_rows * RS;
-  if (lds > 160 * 1024 || hmax > MRF_HMAX) return MV_ERR_UNSUPPORTED;
+  MrfPlan g;
+  const int prc = mrf_tile_plan<T, NWAVES, NTW>(metas, nblocks, true, B, Tn, &g);
+  if (prc != MV_OK) return prc;
+  const int nwg = g.nwg, nit = g.nit;
+  const size_t lds = (size_t)g.lds, lds_wide = (size_t)g.lds_wide;
+  const bool wide = g.wide;
   using ST = StT<T>;
   ST* fbuf = reinterpret_cast<ST*>(ws + lay.f);
   ST* xbuf[2] = {reinterpret_cast<ST*>(ws + lay.x[0]), reinterpret_cast<ST*>(ws + lay.x[1])};
   float* part5 = reinterpret_cast<float*>(ws + lay.part5);
   float* part8 = part5 + (size_t)B * nwg * 32;
-  const dim3 grid(nwg, B);
-  // fp32: the statistics-of-v passes (1, 4) keep only the branch-conv fragments in LDS and run 32-step wave tiles (see the kernel);
-  // same workgroup count, half the iterations, so the partial-sum buffers line up with the 16-step passes
-  constexpr bool WIDE_OK = (M::ES == 4) && NTW == 1;
-  const size_t lds_wide = (size_t)MRF_CONV_FRAGS * FS + MRF_TAB_FLOATS * 4 + (32 + 16) * 4 + (size_t)NWAVES * 32 * 4 +
-                          ((size_t)NWAVES * 2 * 16 + 2 * hmax) * RS;
-  const bool wide = WIDE_OK && nit >= 2 && nit % 2 == 0 && lds_wide <= 160 * 1024 && Tn % (NWAVES * 32) == 0;
+  const dim3 grid(g.gx, g.gy);
+  constexpr bool WIDE_OK = (M::ES == 4) && NTW == 1;   // the wide pass (mrf_tile_plan) exists for this instantiation
+  if (plan) {                                        // the dry run: what the lines below would launch, and the tail they would hand on
+    g.kind = kind;
+    g.launches = 2 * nblocks + (kind == MATERIALIZE || kind == TAIL_WITH_AB ? 1 : 0);
+    *plan = g;
+    const ST* xl = nblocks > 1 ? xbuf[(nblocks - 1) & 1] : (const ST*)r.x;
+    if (kind == TAIL_WITH_AB) *tail = MrfChainTail{fbuf, xl, MRF_ROWS_FP32, nullptr, nullptr, 0};
+    else if (kind != MATERIALIZE) *tail = MrfChainTail{fbuf, xl, MRF_ROWS_FP32, part8, nullptr, nwg};
+    return MV_OK;
+  }
   const ST* xi = (const ST*)r.x;                     // x_i: the input of block i
   for (int i = 0; i < nblocks; ++i) {
-    const bool stdm = mrf_meta_is_std(metas[i]);
+    const bool stdm = (g.std_mask >> i) & 1;
     const char* pk = (const char*)packed[i];
     if (i == 0) {
       if (wide)
@@ -878,9 +911,11 @@ extern "C" int mv_mrf_pack(const mv_mrf_params* params, int param_dtype, const i
   return MV_OK;
 }
 
-extern "C" int mv_mrf_block_fwd_cl(const void* x, void* out, const void* packed, const int* dilations, void* workspace,
-                                   const uint8_t* dropout_mask, float mask_scale, int B, int T_, float eps, int dtype,
-                                   void* stream) {
+// The block entry behind its name: argument checks, the instantiation per storage type, the launches - or, with `plan`, only what
+// those launches would be (no HIP call).
+static int mrf_block_run(const void* x, void* out, const void* packed, const int* dilations, void* workspace,
+                         const uint8_t* dropout_mask, float mask_scale, int B, int T_, float eps, int dtype, void* stream,
+                         MrfPlan* plan) {
   MV_CHECK_ARG(x && out && packed && dilations && workspace && B > 0 && B <= 65535 && T_ > 0 && x != out);
   MV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)packed & 15) == 0);
   MrfMeta meta;
@@ -888,19 +923,26 @@ extern "C" int mv_mrf_block_fwd_cl(const void* x, void* out, const void* packed,
   int rc;
   switch (dtype) {
     case MV_F32:
-      // 8 waves x 16 steps (two waves per SIMD overlap each other's LDS / VALU phases: 150 -> 134 us per block at C2); wide
-      // dilations (halo > 5) do not fit 160 KB next to the hi+lo weight images: 4 waves x 32 steps, same 128-step workgroup tile
-      rc = mrf_launch<float, 8, 1>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream);
+      // 8 waves x 16 steps (two waves per SIMD overlap each other's LDS / VALU phases: 150 -> 134 us per block at C2).  Where that
+      // tile does not fit 160 KB next to the hi+lo weight images: 4 waves x 32 steps, same 128-step workgroup tile - with halos up
+      // to MRF_HMAX = 8 it always fits (138176 + 576 x halo bytes, tests/test_host_mrf_plan.py), so the second line is never taken
+      rc = mrf_launch<float, 8, 1>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream, plan);
       if (rc == MV_ERR_UNSUPPORTED)
-        rc = mrf_launch<float, 4, 2>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream);
+        rc = mrf_launch<float, 4, 2>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream, plan);
       break;
-    case MV_BF16: rc = mrf_launch<bf16, 8, 4>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream); break;
-    case MV_F16: rc = mrf_launch<f16, 8, 4>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream); break;
+    case MV_BF16: rc = mrf_launch<bf16, 8, 4>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream, plan); break;
+    case MV_F16: rc = mrf_launch<f16, 8, 4>(x, out, packed, meta, (float*)workspace, dropout_mask, mask_scale, B, T_, eps, (hipStream_t)stream, plan); break;
     default: return MV_ERR_DTYPE;
   }
-  if (rc != MV_OK) return rc;
+  if (rc != MV_OK || plan) return rc;
   MV_LAUNCH_CHECK();
   return MV_OK;
+}
+
+extern "C" int mv_mrf_block_fwd_cl(const void* x, void* out, const void* packed, const int* dilations, void* workspace,
+                                   const uint8_t* dropout_mask, float mask_scale, int B, int T_, float eps, int dtype,
+                                   void* stream) {
+  return mrf_block_run(x, out, packed, dilations, workspace, dropout_mask, mask_scale, B, T_, eps, dtype, stream, nullptr);
 }
 
 extern "C" size_t mv_mrf_chain_workspace_bytes(int B, int T_, int dtype) { return mrf_chain_ws(B, T_, dtype).total; }
@@ -923,14 +965,14 @@ static int mrf_chain_request(const void* x, void* out, const void* const* packed
 }
 
 // The one dispatcher of the chain: storage dtype -> form and tile geometry (see mrf_tile_t).  *tail is filled unless kind is MATERIALIZE.
-static int mrf_chain_run(const MrfChainReq& r, MrfChainKind kind, MrfChainTail* tail) {
+static int mrf_chain_run(const MrfChainReq& r, MrfChainKind kind, MrfChainTail* tail, MrfPlan* plan = nullptr) {
   const MrfChainWs lay = mrf_chain_ws(r.B, r.T, r.dtype);
   int rc;
   switch (r.dtype) {
     case MV_F32:
-      // wide dilations (halo > 5) do not fit 160 KB next to the hi+lo weight images: 4 waves x 32 steps, same 128-step workgroup tile
-      rc = mrf_chain_launch<float, 8, 1>(r, lay, kind, tail);
-      if (rc == MV_ERR_UNSUPPORTED) rc = mrf_chain_launch<float, 4, 2>(r, lay, kind, tail);
+      // as in the block entry: 4 waves x 32 steps where the 8 x 16 tile does not fit (never, with halos up to MRF_HMAX)
+      rc = mrf_chain_launch<float, 8, 1>(r, lay, kind, tail, plan);
+      if (rc == MV_ERR_UNSUPPORTED) rc = mrf_chain_launch<float, 4, 2>(r, lay, kind, tail, plan);
       break;
     case MV_F32_W16: {
       // every block with the dilations (1, 3, 5): the streaming form (mrf_stream.hip), else the tile form.  The streaming form has no
@@ -938,27 +980,28 @@ static int mrf_chain_run(const MrfChainReq& r, MrfChainKind kind, MrfChainTail* 
       bool all_std = true;
       for (int i = 0; i < r.nblocks; ++i) all_std = all_std && mrf_meta_is_std(r.metas[i]);
       if (all_std && kind != TAIL_WITH_AB) {
-        rc = mvi_mrf_chain_stream(r.x, r.out, r.packed, r.nblocks, r.ws, lay, r.B, r.T, r.eps, r.stream, r.x_pair_in, tail);
+        rc = mvi_mrf_chain_stream(r.x, r.out, r.packed, r.nblocks, r.ws, lay, r.B, r.T, r.eps, r.stream, r.x_pair_in, tail, plan);
+        if (plan && rc == MV_OK) { plan->kind = kind; plan->out_family = -1; plan->row_form = -1; }
         if (rc != MV_ERR_UNSUPPORTED) break;
       }
       if (r.x_pair_in) return MV_ERR_UNSUPPORTED;
-      rc = mrf_chain_launch<f32w16, 8, 2>(r, lay, kind, tail);
+      rc = mrf_chain_launch<f32w16, 8, 2>(r, lay, kind, tail, plan);
       break;
     }
-    case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(r, lay, kind, tail); break;
-    case MV_F16: rc = mrf_chain_launch<f16, 8, 4>(r, lay, kind, tail); break;
+    case MV_BF16: rc = mrf_chain_launch<bf16, 8, 4>(r, lay, kind, tail, plan); break;
+    case MV_F16: rc = mrf_chain_launch<f16, 8, 4>(r, lay, kind, tail, plan); break;
     default: return MV_ERR_DTYPE;
   }
-  if (rc != MV_OK) return rc;
+  if (rc != MV_OK || plan) return rc;
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
 
 // chain + the generator's output projection (Conv1d(64,1,ks,pad ks/2) + activation): the last block's output is formed inside the
 // output conv's staging loop and never stored
-extern "C" int mv_mrf_chain_out_fwd_cl(const void* x, void* wave, const void* const* packed, const int* dilations, int nblocks,
-                                       void* workspace, const void* conv_packed, float conv_bias, int ks, int act, int B, int T_,
-                                       float eps, int dtype, void* stream) {
+static int mrf_chain_out_run(const void* x, void* wave, const void* const* packed, const int* dilations, int nblocks,
+                             void* workspace, const void* conv_packed, float conv_bias, int ks, int act, int B, int T_,
+                             float eps, int dtype, void* stream, MrfPlan* plan) {
   MV_CHECK_ARG(wave && conv_packed && ks > 0 && (ks & 1));
   MrfChainReq r;
   int rc = mrf_chain_request(x, nullptr, packed, dilations, nblocks, workspace, B, T_, eps, dtype, stream, &r);
@@ -967,24 +1010,63 @@ extern "C" int mv_mrf_chain_out_fwd_cl(const void* x, void* wave, const void* co
   // the output conv forms the last block's affine itself where it can: one launch less
   const MrfChainKind kind = mvi_conv_out_affine_takes_partials(cdt, ks) ? TAIL_WITH_PARTIALS : TAIL_WITH_AB;
   MrfChainTail tail;
-  rc = mrf_chain_run(r, kind, &tail);
+  rc = mrf_chain_run(r, kind, &tail, plan);
   if (rc != MV_OK) return rc;
   // conv_packed = mv_conv_out_pack_all image: the fp32 [ks][64] weights come first
   const float* ab = reinterpret_cast<const float*>(r.ws + mrf_chain_ws(B, T_, r.dtype).ab);
-  rc = mvi_conv_out_affine(tail, ab, (const float*)conv_packed, conv_bias, wave, B, T_, MRF_C, ks, ks / 2, act, cdt, eps, r.stream);
-  if (rc != MV_OK) return rc;
+  rc = mvi_conv_out_affine(tail, ab, (const float*)conv_packed, conv_bias, wave, B, T_, MRF_C, ks, ks / 2, act, cdt, eps, r.stream, plan);
+  if (rc != MV_OK || plan) return rc;
   MV_LAUNCH_CHECK();
   return MV_OK;
 }
 
+extern "C" int mv_mrf_chain_out_fwd_cl(const void* x, void* wave, const void* const* packed, const int* dilations, int nblocks,
+                                       void* workspace, const void* conv_packed, float conv_bias, int ks, int act, int B, int T_,
+                                       float eps, int dtype, void* stream) {
+  return mrf_chain_out_run(x, wave, packed, dilations, nblocks, workspace, conv_packed, conv_bias, ks, act, B, T_, eps, dtype, stream,
+                           nullptr);
+}
+
 // out == NULL: the chain's passes run and leave (f, x, partial sums) in the workspace, nothing is materialised (bench.py times the
 // passes the generator really runs this way: its last block's output is formed inside the output conv)
-extern "C" int mv_mrf_chain_fwd_cl(const void* x, void* out, const void* const* packed, const int* dilations, int nblocks,
-                                   void* workspace, int B, int T_, float eps, int dtype, void* stream) {
+static int mrf_chain_fwd_run(const void* x, void* out, const void* const* packed, const int* dilations, int nblocks,
+                             void* workspace, int B, int T_, float eps, int dtype, void* stream, MrfPlan* plan) {
   MV_CHECK_ARG(((uintptr_t)out & 15) == 0);
   MrfChainReq r;
   const int rc = mrf_chain_request(x, out, packed, dilations, nblocks, workspace, B, T_, eps, dtype, stream, &r);
   if (rc != MV_OK) return rc;
   MrfChainTail tail;
-  return mrf_chain_run(r, out ? MATERIALIZE : PASSES_ONLY, &tail);
+  return mrf_chain_run(r, out ? MATERIALIZE : PASSES_ONLY, &tail, plan);
+}
+
+extern "C" int mv_mrf_chain_fwd_cl(const void* x, void* out, const void* const* packed, const int* dilations, int nblocks,
+                                   void* workspace, int B, int T_, float eps, int dtype, void* stream) {
+  return mrf_chain_fwd_run(x, out, packed, dilations, nblocks, workspace, B, T_, eps, dtype, stream, nullptr);
+}
+
+// The dry run of the four entries above for a geometry: the entry's return code for valid, aligned pointers and, for MV_OK, the plan
+// (MrfPlan, in its field order).  Pure host code: the launchers return before their first HIP call when they are given a plan.
+extern "C" int mv_mrf_plan(int entry, int B, int T_, int nblocks, const int* dilations, int dtype, int ks, int* out) {
+  MV_CHECK_ARG(out && dilations && entry >= 0 && entry <= 3);
+  alignas(256) static char dx[256], dy[256], dw[256], dp[256];     // stand-ins for valid pointers: compared and offset, never read
+  const void* packs[8] = {dp, dp, dp, dp, dp, dp, dp, dp};
+  MrfPlan plan = {};
+  int rc;
+  switch (entry) {
+    case 0:
+      MV_CHECK_ARG(nblocks == 1);
+      rc = mrf_block_run(dx, dy, dp, dilations, dw, nullptr, 1.f, B, T_, 1e-5f, dtype, nullptr, &plan);
+      break;
+    case 1: rc = mrf_chain_fwd_run(dx, dy, packs, dilations, nblocks, dw, B, T_, 1e-5f, dtype, nullptr, &plan); break;
+    case 2: rc = mrf_chain_fwd_run(dx, nullptr, packs, dilations, nblocks, dw, B, T_, 1e-5f, dtype, nullptr, &plan); break;
+    default:
+      rc = mrf_chain_out_run(dx, dy, packs, dilations, nblocks, dw, dp, 0.f, ks, MV_ACT_NONE, B, T_, 1e-5f, dtype, nullptr, &plan);
+      break;
+  }
+  if (rc != MV_OK) return rc;
+  const int v[20] = {plan.form, plan.nwaves, plan.ntw, plan.std_mask, plan.nwg, plan.nit, plan.wide, plan.tpw, plan.L, plan.lds,
+                     plan.lds_wide, plan.lds_stat, plan.gx, plan.gy, plan.kind, plan.out_family, plan.row_form, plan.launches,
+                     plan.hmax, plan.out_lds};
+  for (int i = 0; i < 20; ++i) out[i] = v[i];
+  return MV_OK;
 }

@@ -618,19 +618,25 @@ __global__ __launch_bounds__(256) void mrf_stream_final_kernel(const float* __re
   }
 }
 
-static inline void sr_geometry(int B, int Tn, int* L, int* nwg) {
+static inline void sr_geometry(int B, int Tn, int* tpw_, int* L, int* nwg) {
   const int tiles = cdiv(Tn, 16);
   const int wgs = 256 / B > 1 ? 256 / B : 1;          // workgroups per sample that fill the chip once
   int tpw = cdiv(tiles, wgs * SR_NW);
   if (tpw < 1) tpw = 1;
+  *tpw_ = tpw;
   *L = tpw * 16;
   *nwg = cdiv(tiles, tpw * SR_NW);
+}
+
+// dynamic LDS of a pass: FULL = F0 / F (all weight fragments), otherwise V0 / A (the branch convs only)
+static constexpr size_t sr_lds_bytes(bool full) {
+  return (size_t)(full ? SR_WB_ALL : SR_WB_CONV) + MRF_TAB_FLOATS * 4 + (32 + 16 + SR_NW * 32) * 4 + 512 * 8 + (size_t)SR_NW * SR_RING;
 }
 
 template <int MODE, bool XPAIR, bool HL = false>
 static void sr_launch(const SrArgs& a, int B, hipStream_t stream) {
   constexpr bool FULL = (MODE == SM_F0 || MODE == SM_F);
-  const size_t lds = (size_t)(FULL ? SR_WB_ALL : SR_WB_CONV) + MRF_TAB_FLOATS * 4 + (32 + 16 + SR_NW * 32) * 4 + 512 * 8 + (size_t)SR_NW * SR_RING;
+  const size_t lds = sr_lds_bytes(FULL);
   auto k = mrf_stream_kernel<MODE, XPAIR, HL>;
   static bool set = false;
   if (!set) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
@@ -645,10 +651,10 @@ using namespace mv;
 // dilations (1, 3, 5).  ws / lay: the chain's workspace and its layout (mrf_chain_ws).  out != nullptr: fp32 rows of the last block's
 // output are written; otherwise *tail is filled for the fused output conv.
 int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, int nblocks, char* ws, const MrfChainWs& lay, int B, int Tn,
-                         float eps, hipStream_t stream, bool x_pair_in, MrfChainTail* tail) {
+                         float eps, hipStream_t stream, bool x_pair_in, MrfChainTail* tail, MrfPlan* plan) {
   if ((size_t)Tn * SR_ROWB >= (1ull << 31)) return MV_ERR_UNSUPPORTED;     // 32-bit buffer offsets
-  int L, nwg;
-  sr_geometry(B, Tn, &L, &nwg);
+  int tpw, L, nwg;
+  sr_geometry(B, Tn, &tpw, &L, &nwg);
   float* fbuf = reinterpret_cast<float*>(ws + lay.f);
   char* xbuf[2] = {ws + lay.x[0], ws + lay.x[1]};
   float* part5 = reinterpret_cast<float*>(ws + lay.part5);
@@ -658,6 +664,19 @@ int mvi_mrf_chain_stream(const void* x, void* out, const void* const* packed, in
   const void* xi = x;
   bool xi_pair = x_pair_in;                    // the producer already wrote pair rows (the last upsampler's streaming kernel)
   const bool hl = !xi_pair;                   // hl8 rows between the blocks (pair-row input keeps pair rows)
+  if (plan) {                                 // the dry run: what the lines below would launch, and the tail they would hand on
+    plan->form = 1; plan->nwaves = SR_NW; plan->ntw = 1; plan->std_mask = (1 << nblocks) - 1;
+    plan->nwg = nwg; plan->nit = 0; plan->wide = 0; plan->tpw = tpw; plan->L = L;
+    plan->lds = (int)sr_lds_bytes(true); plan->lds_wide = 0; plan->lds_stat = (int)sr_lds_bytes(false);
+    plan->gx = nwg; plan->gy = B; plan->hmax = SR_H;
+    plan->launches = 2 * nblocks + (out ? 1 : 0);
+    if (!out) {
+      const bool pair_last = x_pair_in || nblocks > 1;
+      *tail = MrfChainTail{fbuf, nblocks > 1 ? (const void*)xbuf[(nblocks - 1) & 1] : x,
+                           !hl ? MRF_ROWS_PAIR : pair_last ? MRF_ROWS_HL8 : MRF_ROWS_FP32, part8, nullptr, nwg};
+    }
+    return MV_OK;
+  }
   for (int i = 0; i < nblocks; ++i) {
     a.packed = (const char*)packed[i];
     if (i == 0) {

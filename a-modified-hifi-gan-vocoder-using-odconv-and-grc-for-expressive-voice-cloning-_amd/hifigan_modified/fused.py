@@ -53,12 +53,9 @@ class MrfFused:
             if (g.kernel_size != 3 or g.groups != 4 or g.norm_groups != 5 or g.in_channels != 64
                     or not hasattr(g, "residual_proj")):
                 return False
-        offs = {0}
-        for d in blk.dilations:
-            if not 1 <= d <= 8:
-                return False
-            offs |= {d, -d}
-        return len(offs) <= 7
+        # the dilation set: whatever the block entry's own dry run (mv_mrf_plan, no HIP call) takes in every storage type
+        dil, plan = _INT3(*(int(d) for d in blk.dilations)), (ctypes.c_int * 20)()
+        return all(N.lib().mv_mrf_plan(0, 1, 16, 1, dil, dt, 0, plan) == 0 for dt in (N.MV_F32, N.MV_BF16, N.MV_F16))
 
     def _params(self):
         b = self.blk

@@ -198,6 +198,26 @@ int mv_mrf_chain_fwd_cl(const void* x, void* out, const void* const* packed, con
 int mv_mrf_chain_out_fwd_cl(const void* x, void* wave, const void* const* packed, const int* dilations, int nblocks, void* workspace,
                             const void* conv_packed, float conv_bias, int ks, int act, int B, int T, float eps, int dtype,
                             void* stream);
+/* What the three entry points above would do, asked without a GPU (no HIP call): the entry's return code for this geometry with
+ * valid, aligned pointers and no dropout mask, and for MV_OK the plan in out[0..19].  entry: 0 mv_mrf_block_fwd_cl (nblocks = 1),
+ * 1 mv_mrf_chain_fwd_cl with out, 2 the same with out = NULL (the passes only), 3 mv_mrf_chain_out_fwd_cl with a ks-tap output conv
+ * (ks is ignored otherwise).  dilations: nblocks x 3 ints.  The launchers take their geometry from the function that fills this plan.
+ *   [0] form: 0 tile form (mrf_kernel<T, NWAVES, NTW, PASS, STD>), 1 streaming form (mrf_stream_kernel);
+ *   [1] NWAVES, [2] NTW (16-step column tiles of a wave per iteration; the workgroup tile is NWAVES x NTW x 16 steps; streaming: 8, 1);
+ *   [3] bit i: block i runs STD = true (dilations (1, 3, 5));
+ *   [4] nwg, workgroups per sample; [5] nit, tiles a workgroup walks (streaming: 0); [6] 1 if the fp32 chain's first pass runs
+ *       its wide 32-step form (then over nit / 2 iterations);
+ *   [7] tpw, [8] L: column tiles and time steps of a wave's span in the streaming form (tile form: 0);
+ *   [9] dynamic LDS bytes of the passes (streaming: of the passes F0 / F), [10] of the wide pass (0 without one), [11] streaming: of
+ *       the passes V0 / A;
+ *   [12], [13] grid x, y of the passes;
+ *   [14] how the chain ends: 0 MATERIALIZE (its own last pass writes out), 1 PASSES_ONLY, 2 TAIL_WITH_AB (mrf_affine_kernel writes
+ *        the last block's deferred affine for the output conv), 3 TAIL_WITH_PARTIALS (the output conv forms it from the partial
+ *        sums); -1 for the block entry;
+ *   [15] output conv: -1 none, 0 conv_out_affine_kernel<T, 64>, 1 conv_out_affine_mfma_kernel<64, rows>; [16] the rows it reads x
+ *        in: 0 fp32 rows, 1 pair rows, 4 hl8 rows, -1 none;
+ *   [17] kernel launches of the call; [18] the largest halo of the blocks; [19] dynamic LDS bytes of the output conv. */
+int mv_mrf_plan(int entry, int B, int T, int nblocks, const int* dilations, int dtype, int ks, int* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused ODConv1d / ODConvTranspose1d, channels-last.   replaces odconv.py:73-108 / :172-205 (attention ->

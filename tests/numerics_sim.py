@@ -85,18 +85,29 @@ def chain_sim(x, sds, n, mode, dilations=(1, 3, 5)):
     """n chained MultiReceptiveFieldBlocks (state dicts `sds`, x [B, 64, T] fp32) with the roundings of one MrfChain entry:
     three     forward_cl(x): three bf16 pieces per operand, fp32 rows between the blocks
     w16       forward_cl(x, w16=True): f16 hi + lo operands x single-f16 weights, hl8 rows between the blocks (x' and f)
-    w16_pair  forward_cl(pair rows, w16=True, x_pair=True): the same with pair rows in, between the blocks and out."""
+    w16_pair  forward_cl(pair rows, w16=True, x_pair=True): the same with pair rows in, between the blocks and out
+    w16_tile  forward_cl(x, w16=True) at dilations other than (1, 3, 5): the tile form of the same operands, fp32 rows throughout
+    fp16/bf16 forward_cl(x in 16-bit storage): weights, operands, the concat and every stored row in that type (x is rounded first).
+    dilations: one set for every block, or one set per block."""
+    per_block = isinstance(dilations[0], (tuple, list))
     with torch.no_grad():
         if mode == "w16_pair":
             x = pair(x)
+        elif mode in ("fp16", "bf16"):
+            x = EB.q(x, mode)
         for i in range(n):
             last = i == n - 1
+            dil = tuple(dilations[i]) if per_block else dilations
             if mode == "three":
-                x = EB.mrf_forward(x, sds[i], "", dilations, "bf16x3", "bf16x3", "fp32", opmode="bf16x3")
+                x = EB.mrf_forward(x, sds[i], "", dil, "bf16x3", "bf16x3", "fp32", opmode="bf16x3")
             elif mode == "w16":
-                x = EB.mrf_forward(x, sds[i], "", dilations, "fp16", "fp16x2", "fp32" if last else "hl8", opmode="fp16x2", fmode="hl8")
+                x = EB.mrf_forward(x, sds[i], "", dil, "fp16", "fp16x2", "fp32" if last else "hl8", opmode="fp16x2", fmode="hl8")
             elif mode == "w16_pair":
-                x = EB.mrf_forward(x, sds[i], "", dilations, "fp16", "fp16x2", "fp16x2", opmode="fp16x2")
+                x = EB.mrf_forward(x, sds[i], "", dil, "fp16", "fp16x2", "fp16x2", opmode="fp16x2")
+            elif mode == "w16_tile":
+                x = EB.mrf_forward(x, sds[i], "", dil, "fp16", "fp16x2", "fp32", opmode="fp16x2")
+            elif mode in ("fp16", "bf16"):
+                x = EB.mrf_forward(x, sds[i], "", dil, mode, mode, mode)
             else:
                 raise ValueError(mode)
     return x

@@ -32,8 +32,11 @@ def _blocks(H, seed=0):
 
 @pytest.mark.parametrize("B,T", [(2, 48), (3, 700), (1, 16), (1, 17), (5, 1000), (2, 4100), (2, 8192)])
 def test_stream_chain_vs_oracle_ragged(H, B, T):
-    """1, 2 and 3 chained blocks on ragged shapes (partial last tile, waves without work, one-tile spans, several workgroups per
-    sample): against the oracle's blocks, bit-reproducible, and equal to the tile form of the same operand mode to fp32 rounding."""
+    """1, 2 and 3 chained blocks on ragged shapes: against the oracle's blocks, bit-reproducible, and close to the three-product tile
+    form of the same chain.  What these shapes reach (mv_mrf_plan, tests/test_host_mrf_plan.py): a partial last column tile, waves
+    without work, several workgroups per sample - and ONE-tile spans only: every shape plans tpw = 1, L = 16 in the streaming form
+    and nit = 1 in the tile form, so the ring of three slots never wraps and no workgroup walks a second tile here.  Multi-tile
+    spans, spans that end inside a column tile and workgroups with idle iterations are in tests/test_gpu_mrf_arms.py."""
     from hifigan_modified.fused import MrfChain, mrf_fused_for
     blks, sds = _blocks(H)
     chain = MrfChain([mrf_fused_for(bk) for bk in blks])

@@ -23,19 +23,18 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const T* __restrict__ gy, 
 // ------------------------------------------------------------------------------------------- conv weight gradient
 // conv1d:  y[b,o,t] = sum_{c,j} w[o,c,j] x[b,c,t*stride - pad + j*dil]   (groups = 1)
 // gws[b?][o][c][j] = sum_t gy[b,o,t] x[b,c,t*stride-pad+j*dil]
-// One workgroup = 16(o) x 16(c) weight tile, all taps (ks <= 16), looping over time; per-sample results are
-//   nbanks == 1: gw [Cout][Cin][ks] += tile
-//   nbanks  > 1: gw[k] += alpha[b,k] * tile ;  galpha[b,k] += <tile, w[k] tile>   (both linear in the tile, so partial
-//                time chunks can be added independently; fp32 atomics)
+// One workgroup = 16(o) x 16(c) weight tile, all taps (ks <= 16), looping over one time chunk of one sample; its tile goes to
+//   per_sample == 0 (nbanks == 1): gw [Cout][Cin][ks] += tile (fp32 atomics into a zero-filled gw)
+//   per_sample == 1 (nbanks  > 1): gw [B][Cout][Cin][ks], the sample's own tile: stored when the sample has one chunk, added with
+//                fp32 atomics into a zero-filled buffer otherwise.  odconv_wgrad_reduce(4)_kernel applies the alpha chain.
 constexpr int WG_TT = 64;
 constexpr int WG_MAXKS = 16;
 
 template <typename T>
 __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ gy,
-                                                           const T* __restrict__ w, const float* __restrict__ alpha,
-                                                           float* __restrict__ gw, float* __restrict__ galpha,
+                                                           float* __restrict__ gw,
                                                            int B, int Cin, int Tin, int Cout, int Tout, int ks,
-                                                           int stride, int pad, int dil, int nbanks,
+                                                           int stride, int pad, int dil,
                                                            long x_bs, long x_cs, long g_bs, long g_cs, int tsplit, int tchunk,
                                                            int per_sample) {
   // grid.z = B * tsplit: every workgroup reduces one (sample, time chunk) and adds its tile with fp32 atomics
@@ -43,7 +42,6 @@ __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const T* __restrict__
   const int xw = (WG_TT - 1) * stride + (ks - 1) * dil + 1;
   float* xs = sm;                 // [16][xw]
   float* gs = sm + 16 * xw;       // [16][WG_TT]
-  float* red = gs + 16 * WG_TT;   // [32]
   const int tid = threadIdx.x, ol = tid >> 4, cl = tid & 15;
   const int o = blockIdx.y * 16 + ol, c = blockIdx.x * 16 + cl;
   const long wbank = (long)Cout * Cin * ks;
@@ -80,27 +78,11 @@ __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const T* __restrict__
       for (int j = 0; j < WG_MAXKS; ++j)
         if (j < ks) { if (tsplit == 1) gwk[j] = acc[j]; else atomicAdd(gwk + j, acc[j]); }
     }
-  } else if (nbanks == 1) {
-    if (ok) {
-      float* gwk = gw + ((long)o * Cin + c) * ks;
+  } else if (ok) {
+    float* gwk = gw + ((long)o * Cin + c) * ks;
 #pragma unroll
-      for (int j = 0; j < WG_MAXKS; ++j)
-        if (j < ks) atomicAdd(gwk + j, acc[j]);
-    }
-  } else {
-    for (int k = 0; k < nbanks; ++k) {
-      const float a = alpha[b * nbanks + k];
-      float dot = 0.f;
-      if (ok) {
-        float* gwk = gw + k * wbank + ((long)o * Cin + c) * ks;
-        const T* wk = w + k * wbank + ((long)o * Cin + c) * ks;
-#pragma unroll
-        for (int j = 0; j < WG_MAXKS; ++j)
-          if (j < ks) { atomicAdd(gwk + j, a * acc[j]); dot += acc[j] * ld<T>(wk + j); }
-      }
-      dot = block_sum(dot, red);
-      if (tid == 0) atomicAdd(galpha + b * nbanks + k, dot);
-    }
+    for (int j = 0; j < WG_MAXKS; ++j)
+      if (j < ks) atomicAdd(gwk + j, acc[j]);
   }
 }
 
@@ -357,7 +339,9 @@ __global__ __launch_bounds__(256) void gn_pre_bwd_kernel(const T* __restrict__ x
     else if (act == ACT_TANH) { const float th = tanhf(z); d = 1.f - th * th; }
     return d;
   };
-  if (sizeof(T) == 2 && all_mult8(Tn, x_bs, x_cs, g_bs, g_cs) && (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0) {
+  // the mask is read as 8-byte words: its address is part of the predicate (Tn % 8 == 0 keeps every row of an aligned mask aligned)
+  if (sizeof(T) == 2 && all_mult8(Tn, x_bs, x_cs, g_bs, g_cs) && (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0 &&
+      ((uintptr_t)mask & 7) == 0) {
     for (int t = (blockIdx.x * blockDim.x + threadIdx.x) * 8; t < Tn; t += gridDim.x * blockDim.x * 8) {
       float gv[8], xv[8];
       load8f<T>(gr + t, gv);
@@ -511,6 +495,7 @@ static inline int grid_for(long n, int block = 256, int cap = 2048) {
 
 extern "C" int mv_act_bwd(const void* gy, const void* y, void* gx, long n, int act, float slope, int dtype, void* stream) {
   MV_CHECK_ARG(gy && y && gx && n > 0);
+  MV_CHECK_ARG(act == ACT_NONE || act == ACT_LRELU || act == ACT_TANH);   // SiLU's derivative needs the pre-activation: mv_groupnorm_bwd
   MV_DISPATCH(dtype, hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
                                         (const T*)gy, (const T*)y, (T*)gx, n, act, slope));
   MV_LAUNCH_CHECK();
@@ -521,36 +506,72 @@ extern "C" size_t mv_conv1d_wgrad_workspace_bytes(int B, int Cin, int Cout, int 
   return nbanks > 1 ? sizeof(float) * (size_t)B * Cout * Cin * ks : 0;
 }
 
-extern "C" int mv_conv1d_wgrad(const void* x, const void* gy, const void* w, const float* alpha, float* gw, float* galpha,
-                               float* workspace, int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad,
-                               int dil, int nbanks, long x_bs, long x_cs, long g_bs, long g_cs, int dtype, void* stream) {
-  MV_CHECK_ARG(x && gy && gw && B > 0 && Cin > 0 && Cout > 0 && Tin > 0 && Tout > 0 && ks > 0 && ks <= WG_MAXKS);
-  MV_CHECK_ARG(nbanks >= 1 && nbanks <= 8 && (nbanks == 1 || (alpha && galpha && w && workspace)));
-  const int xw = (WG_TT - 1) * stride + (ks - 1) * dil + 1;
-  const size_t lds = sizeof(float) * (16 * xw + 16 * WG_TT + 32);
+// What mv_conv1d_wgrad decides from the shape alone: the one statement of it, used by the launcher and handed out by
+// mv_conv1d_wgrad_plan.  Returns the entry point's code for the geometry (MV_OK: *p is filled).
+struct Conv1dWgradPlan {
+  int tsplit, tchunk;        // time chunks per sample, steps per chunk (a multiple of WG_TT)
+  int gx, gy, gz;            // grid: Cin tiles, Cout tiles, B * tsplit
+  int lds;                   // dynamic LDS bytes
+  int zero_fill;             // the destination (gw, or the per-sample workspace) is zero-filled and added to with atomics
+  int per_sample;            // nbanks > 1: per-sample tiles into the workspace, then an alpha-chain reduction
+  int reduce4;               // -1 no reduction; 1 odconv_wgrad_reduce4_kernel when workspace and gw are 16-byte aligned; 0 the generic one
+};
+static bool wgrad_reduce_takes4(int K, long nelem, const void* a, const void* b) {
+  return K <= 4 && nelem % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+}
+static int conv1d_wgrad_plan(int B, int Cin, int Cout, int Tout, int ks, int stride, int dil, int nbanks, Conv1dWgradPlan* p) {
+  MV_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && Tout > 0 && ks > 0 && ks <= WG_MAXKS && stride > 0 && dil > 0);
+  MV_CHECK_ARG(nbanks >= 1 && nbanks <= 8);
+  const long xw = (long)(WG_TT - 1) * stride + (long)(ks - 1) * dil + 1;
+  const size_t lds = sizeof(float) * (16 * (size_t)xw + 16 * WG_TT + 32);
   if (lds > 64 * 1024) return MV_ERR_UNSUPPORTED;
   // split time so that ~2048 workgroups exist; partial tiles are combined with fp32 atomics
   const int tiles = cdiv(Cin, 16) * cdiv(Cout, 16);
-  int tsplit = cdiv(2048, tiles * B);
+  long tsplit = (2048 + (long)tiles * B - 1) / ((long)tiles * B);
   const int max_split = cdiv(Tout, WG_TT);
   if (tsplit > max_split) tsplit = max_split;
   if (tsplit < 1) tsplit = 1;
-  const int tchunk = cdiv(cdiv(Tout, tsplit), WG_TT) * WG_TT;
-  tsplit = cdiv(Tout, tchunk);
-  if ((long)B * tsplit > 65535) return MV_ERR_UNSUPPORTED;
-  dim3 grid(cdiv(Cin, 16), cdiv(Cout, 16), B * tsplit);
+  p->tchunk = cdiv(cdiv(Tout, (int)tsplit), WG_TT) * WG_TT;
+  p->tsplit = cdiv(Tout, p->tchunk);
+  if ((long)B * p->tsplit > 65535) return MV_ERR_UNSUPPORTED;
+  p->gx = cdiv(Cin, 16); p->gy = cdiv(Cout, 16); p->gz = B * p->tsplit;
+  p->lds = (int)lds;
+  p->per_sample = nbanks > 1;
+  p->zero_fill = !p->per_sample || p->tsplit > 1;
+  p->reduce4 = p->per_sample ? (int)wgrad_reduce_takes4(nbanks, (long)Cout * Cin * ks, nullptr, nullptr) : -1;
+  return MV_OK;
+}
+
+extern "C" int mv_conv1d_wgrad_plan(int B, int Cin, int Cout, int Tout, int ks, int stride, int dil, int nbanks, int* out) {
+  MV_CHECK_ARG(out);
+  Conv1dWgradPlan p;
+  const int rc = conv1d_wgrad_plan(B, Cin, Cout, Tout, ks, stride, dil, nbanks, &p);
+  if (rc != MV_OK) return rc;
+  const int v[9] = {p.tsplit, p.tchunk, p.gx, p.gy, p.gz, p.lds, p.zero_fill, p.per_sample, p.reduce4};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return MV_OK;
+}
+
+extern "C" int mv_conv1d_wgrad(const void* x, const void* gy, const void* w, const float* alpha, float* gw, float* galpha,
+                               float* workspace, int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad,
+                               int dil, int nbanks, long x_bs, long x_cs, long g_bs, long g_cs, int dtype, void* stream) {
+  MV_CHECK_ARG(x && gy && gw && Tin > 0);
+  Conv1dWgradPlan p;
+  const int rc = conv1d_wgrad_plan(B, Cin, Cout, Tout, ks, stride, dil, nbanks, &p);
+  if (rc != MV_OK) return rc;
+  MV_CHECK_ARG(nbanks == 1 || (alpha && galpha && w && workspace));
+  dim3 grid(p.gx, p.gy, p.gz);
   const long nelem = (long)Cout * Cin * ks;
-  const int per_sample = nbanks > 1;
-  float* dst = per_sample ? workspace : gw;
+  float* dst = p.per_sample ? workspace : gw;
   // ODConv (nbanks > 1): per-sample tiles first (no cross-sample contention), then one reduction applies the alpha chain
-  if (!per_sample || tsplit > 1)
-    MV_HIP(mvi_zero_async(dst, sizeof(float) * (size_t)(per_sample ? B : 1) * nelem, (hipStream_t)stream));
+  if (p.zero_fill)
+    MV_HIP(mvi_zero_async(dst, sizeof(float) * (size_t)(p.per_sample ? B : 1) * nelem, (hipStream_t)stream));
   MV_DISPATCH(dtype, {
-    hipLaunchKernelGGL(conv1d_wgrad_kernel<T>, grid, dim3(256), lds, (hipStream_t)stream, (const T*)x, (const T*)gy,
-                       (const T*)w, alpha, dst, galpha, B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, nbanks, x_bs, x_cs,
-                       g_bs, g_cs, tsplit, tchunk, per_sample);
-    if (per_sample) {
-      if (nbanks <= 4 && nelem % 4 == 0 && (((uintptr_t)workspace | (uintptr_t)gw) & 15) == 0) {
+    hipLaunchKernelGGL(conv1d_wgrad_kernel<T>, grid, dim3(256), (size_t)p.lds, (hipStream_t)stream, (const T*)x, (const T*)gy,
+                       dst, B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, x_bs, x_cs,
+                       g_bs, g_cs, p.tsplit, p.tchunk, p.per_sample);
+    if (p.per_sample) {
+      if (wgrad_reduce_takes4(nbanks, nelem, workspace, gw)) {
         hipLaunchKernelGGL(odconv_wgrad_reduce4_kernel<T>, dim3((unsigned)((nelem / 4 + 255) / 256)), dim3(256),
                            sizeof(float) * B * nbanks, (hipStream_t)stream, workspace, (const T*)w, alpha, gw, galpha, B, nbanks, nelem);
       } else {
@@ -568,7 +589,7 @@ extern "C" int mv_conv1d_wgrad(const void* x, const void* gy, const void* w, con
 extern "C" int mv_odconv_wgrad_reduce(const float* gws, const void* w, const float* alpha, float* gw, float* galpha, int B, int K,
                                       long nelem, int dtype, void* stream) {
   MV_CHECK_ARG(gws && w && alpha && gw && galpha && B > 0 && K >= 1 && K <= 8 && nelem > 0);
-  if (K <= 4 && nelem % 4 == 0 && (((uintptr_t)gws | (uintptr_t)gw) & 15) == 0) {
+  if (wgrad_reduce_takes4(K, nelem, gws, gw)) {
     MV_DISPATCH(dtype, hipLaunchKernelGGL(odconv_wgrad_reduce4_kernel<T>, dim3((unsigned)((nelem / 4 + 255) / 256)), dim3(256),
                                           sizeof(float) * B * K, (hipStream_t)stream, gws, (const T*)w, alpha, gw, galpha, B, K, nelem));
     MV_LAUNCH_CHECK();
@@ -627,7 +648,7 @@ extern "C" int mv_groupnorm_bwd(const void* x, const void* gy, const float* mean
   const long dense_bs = (long)C * T_, dense_cs = T_;
   MV_DISPATCH(dtype, {
     const bool vec = sizeof(T) == 2 && all_mult8(T_, x_bs, x_cs, g_bs, g_cs) &&
-                     (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)gz_ws | (uintptr_t)gx) & 15) == 0;
+                     (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)gz_ws | (uintptr_t)gx) & 15) == 0 && ((uintptr_t)mask & 7) == 0;
     dim3 ge(grid_for(vec ? cdiv(T_, 8) : T_, 256, 64), B * C);
     hipLaunchKernelGGL(gn_pre_bwd_kernel<T>, ge, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)gy, mean, rstd,
                        (const T*)gw, (const T*)gb, mask, mask_scale, (T*)gz_ws, C, T_, G, act, slope, x_bs, x_cs, g_bs, g_cs);

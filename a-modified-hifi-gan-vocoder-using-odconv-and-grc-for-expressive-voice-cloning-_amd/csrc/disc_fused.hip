@@ -1883,21 +1883,39 @@ extern "C" size_t mv_odconvT_wgrad_workspace_bytes(int B, int Cin, int Cout, int
   return sizeof(float) * n * B + (dtype == MV_F32 ? 4 : 2) * n * K + sizeof(float) * n * K + 1024;
 }
 
+// The shape half of mv_odconvT_wgrad_mfma's contract and its per-sample two-tap plan: the launcher and mv_odconvT_wgrad_plan both ask here.
+// "g" operand = x (rows = input channels), "x" operand = the padded gradient rows, one position longer than Tin; every sample keeps its tile.
+static int odconvT_wgrad_plan(int B, int Tin, int Cin, int Cout, int ks, int stride, int K, int dtype, DconvWgradPlan* pl) {
+  MV_CHECK_ARG(B > 0 && Tin > 0 && Cin > 0 && Cout > 0 && stride > 0 && K >= 1 && K <= 8 && ks == 2 * stride);
+  MV_CHECK_ARG(Cin % 8 == 0 && (stride * Cout) % 8 == 0);
+  if (dtype == MV_F32) return MV_ERR_UNSUPPORTED;
+  return dconv_wgrad_plan(B, 1, Tin, stride * Cout, Cin, 1, 2, 1, dtype, Tin + 1, (long)Cin * Cout * ks, pl);
+}
+
+// out: the twelve integers of mv_dconv_wgrad_plan (see the header) for the per-sample form
+extern "C" int mv_odconvT_wgrad_plan(int B, int Tin, int Cin, int Cout, int ks, int stride, int K, int dtype, int* out) {
+  MV_CHECK_ARG(out);
+  DconvWgradPlan pl;
+  const int rc = odconvT_wgrad_plan(B, Tin, Cin, Cout, ks, stride, K, dtype, &pl);
+  if (rc != MV_OK) return rc;
+  const int v[12] = {pl.three, pl.tw, pl.wt, pl.otile, pl.wsplit, pl.nchunks, pl.cpw, pl.groups, (int)pl.lds, pl.gx, pl.gy, pl.gz};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
+  return MV_OK;
+}
+
 extern "C" int mv_odconvT_wgrad_mfma(const void* x_cl, const void* gp, const void* w, const float* alpha, float* gw, float* galpha,
                                      void* workspace, int B, int Tin, int Cin, int Cout, int ks, int stride, int K, int dtype,
                                      void* stream) {
-  MV_CHECK_ARG(x_cl && gp && w && alpha && gw && galpha && workspace && B > 0 && Tin > 0 && K >= 1 && K <= 8 && ks == 2 * stride);
-  MV_CHECK_ARG(Cin % 8 == 0 && (stride * Cout) % 8 == 0 && ((uintptr_t)x_cl & 15) == 0 && ((uintptr_t)gp & 15) == 0);
-  if (dtype == MV_F32) return MV_ERR_UNSUPPORTED;
+  MV_CHECK_ARG(x_cl && gp && w && alpha && gw && galpha && workspace);
+  MV_CHECK_ARG(((uintptr_t)x_cl & 15) == 0 && ((uintptr_t)gp & 15) == 0);
+  DconvWgradPlan pl;
+  int rc = odconvT_wgrad_plan(B, Tin, Cin, Cout, ks, stride, K, dtype, &pl);
+  if (rc != MV_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)Cin * Cout * ks;
   float* tiles = (float*)workspace;                                           // [B][2][Cin][s*Cout]
   char* wtm = (char*)(tiles + n * B);                                         // [K][2][Cin][s*Cout] in `dtype`
   float* gtm = (float*)(wtm + ((size_t)2 * n * K + 255) / 256 * 256);         // [K][2][Cin][s*Cout] fp32
-  // "g" operand = x (rows = input channels), "x" operand = padded gradient rows (columns = (r, o)), taps q = 0, 1; per-sample tiles
-  DconvWgradPlan pl;
-  int rc = dconv_wgrad_plan(B, 1, Tin, stride * Cout, Cin, 1, 2, 1, dtype, Tin + 1, n, &pl);
-  if (rc != MV_OK) return rc;
   MV_HIP(mvi_zero_async(tiles, sizeof(float) * (size_t)n * B, s));
   const DwgradArgs a{gp, x_cl, tiles, nullptr, B, 1, Tin, stride * Cout, Cin, 1, s};
   const unsigned g1 = grid_cap(n * K, 256, 4096);

@@ -149,6 +149,10 @@ int mv_odconvT_adjoint_weights(const void* kernels, void* out, int K, int Cin, i
 size_t mv_odconvT_wgrad_workspace_bytes(int B, int Cin, int Cout, int ks, int K, int dtype);
 int mv_odconvT_wgrad_mfma(const void* x_cl, const void* gp, const void* w, const float* alpha, float* gw, float* galpha,
                           void* workspace, int B, int Tin, int Cin, int Cout, int ks, int stride, int K, int dtype, void* stream);
+/* What mv_odconvT_wgrad_mfma would do, asked without a GPU (no HIP call): its return code for this geometry with valid, aligned
+ * pointers, and for MV_OK the twelve integers of mv_dconv_wgrad_plan in out[0..11] for its per-sample two-tap form
+ * (dconv_wgrad_kernel<T,1,2,128>: family 0, TW 2; one workgroup per (tile, sample) walks all of the sample's chunks, grid z = B). */
+int mv_odconvT_wgrad_plan(int B, int Tin, int Cin, int Cout, int ks, int stride, int K, int dtype, int* out);
 int mv_odconv_wgrad_reduce(const float* gws, const void* w, const float* alpha, float* gw, float* galpha, int B, int K,
                            long nelem, int dtype, void* stream);
 
@@ -311,7 +315,8 @@ int mv_conv_out_act_packed_cl(const void* x, const void* packed, float bias, voi
  * (autograd of F.conv1d / F.conv_transpose1d / F.conv2d at odconv.py:95-99,192-197, grc_lora.py:33,57,66,160,
  *  discriminators.py:57-65,97-107) */
 
-/* gx = gy * act'(z), expressed through the activation OUTPUT y (LeakyReLU: sign(y); tanh: 1-y^2). */
+/* gx = gy * act'(z), expressed through the activation OUTPUT y (LeakyReLU: y >= 0 ? 1 : slope, so 1 at +0 and -0; tanh: 1-y^2).
+ * ACT_SILU is refused (MV_ERR_ARG): its derivative needs the pre-activation, which mv_groupnorm_bwd recomputes. */
 int mv_act_bwd(const void* gy, const void* y, void* gx, long n, int act, float slope, int dtype, void* stream);
 
 /* conv1d weight gradient (groups = 1, ks <= 16).  y = conv1d(x, w[nbanks][Cout][Cin][ks], alpha).
@@ -324,6 +329,13 @@ size_t mv_conv1d_wgrad_workspace_bytes(int B, int Cin, int Cout, int ks, int nba
 int mv_conv1d_wgrad(const void* x, const void* gy, const void* w, const float* alpha, float* gw, float* galpha,
                     float* workspace, int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil, int nbanks,
                     long x_bs, long x_cs, long g_bs, long g_cs, int dtype, void* stream);
+/* What mv_conv1d_wgrad would do, asked without a GPU (no HIP call): its return code for this geometry with valid pointers, and for
+ * MV_OK the plan in out[0..8]: [0] tsplit, time chunks per sample; [1] tchunk, steps per chunk (a multiple of 64); [2..4] grid x, y, z
+ * (Cin tiles, Cout tiles, B * tsplit; 256 threads); [5] dynamic LDS bytes; [6] 1 if the destination (gw, or the per-sample
+ * workspace) is zero-filled and added to with atomics, 0 if every element is stored once; [7] 1 for the per-sample form (nbanks > 1);
+ * [8] the alpha-chain reduction: -1 none, 1 odconv_wgrad_reduce4_kernel (taken when workspace and gw are 16-byte aligned), 0 the
+ * generic kernel.  The launcher takes its geometry from the function that fills this plan. */
+int mv_conv1d_wgrad_plan(int B, int Cin, int Cout, int Tout, int ks, int stride, int dil, int nbanks, int* out);
 /* gbias[k][o] = sum_b alpha[b,k] sum_t gy[b,o,t]; galpha[b,k] += sum_o (sum_t gy[b,o,t]) bias[k][o] (K > 1).
  * rowsum_ws: fp32 [B*C] scratch. */
 int mv_bias_grad(const void* gy, const float* alpha, const void* bias, float* rowsum_ws, float* gbias, float* galpha,

@@ -20,6 +20,7 @@ test_gpu_grads.py; 16-bit bounds are 2-3x the error measured on the MI355X (both
 import pytest
 import torch
 
+from backward_cases import wgrad_tsplit as _wgrad_tsplit     # host rule of mv_conv1d_wgrad: time chunks per (sample, tile); 1 = direct store
 from oracle import vocoder_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -50,14 +51,6 @@ def _round_params_(mod, dtype):
 
 def _ref_params(mod, names):
     return {k: p.detach().to(REF, torch.float64).requires_grad_(True) for k, p in mod.named_parameters() if k in names}
-
-
-def _wgrad_tsplit(B, Cin, Cout, Tout):
-    """Host rule of mv_conv1d_wgrad (csrc/backward.hip): time split per (sample, tile); 1 = the per-sample direct store."""
-    cdiv = lambda a, b: -(-a // b)
-    tiles = cdiv(Cin, 16) * cdiv(Cout, 16)
-    t = max(1, min(cdiv(2048, tiles * B), cdiv(Tout, 64)))
-    return cdiv(Tout, cdiv(cdiv(Tout, t), 64) * 64)
 
 
 def _check(errs, tols, tag):

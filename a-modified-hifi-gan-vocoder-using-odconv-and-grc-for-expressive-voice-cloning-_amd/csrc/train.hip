@@ -4,6 +4,7 @@
 //   AdamW:    conditioned_hifigan.py:219 (torch.optim.AdamW semantics: decoupled weight decay, bias correction)
 //   mel loss: defined by this build (the reference only has placeholders)
 #include "common.h"
+#include "philox.h"
 #include <cstdlib>
 
 namespace mv {
@@ -11,16 +12,7 @@ namespace mv {
 // ------------------------------------------------------------------------------------------- dropout keep-mask (Philox4x32-10)
 // mask[i] = 1 with probability 1-p (nn.Dropout of grc_lora.py:151,162).  Counter-based: element block i/8 is counter (i/8, 0, 0, 0)
 // under key (seed lo, seed hi), 16 random bits per element - the mask depends only on (seed, index), not on the launch geometry.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// philox4x32_10 itself is in philox.h (the clip sampler's noise draws from it too).
 __global__ __launch_bounds__(256) void dropout_mask_kernel(uint8_t* __restrict__ mask, long n, uint32_t thresh16, uint32_t k0, uint32_t k1) {
   const long nblk = (n + 7) / 8;
   for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblk; blk += (long)gridDim.x * blockDim.x) {

@@ -15,6 +15,7 @@ from .streaming import ChunkedVocoder
 from .data import MelFrontEnd, ClipSampler
 from .plain_hifigan import PlainHiFiGANGenerator
 from .embedding_extractors import ECAPA_TDNN, SE_Res2Block, SE_Module, Emotion2Vec, EmbeddingExtractor
+from .data import DeviceClipSampler, resample_table
 
 __all__ = [
     "ODConv1d", "ODConvTranspose1d", "GRC_LoRA_Block", "FiLMLayer", "MultiReceptiveFieldBlock",
@@ -23,4 +24,5 @@ __all__ = [
     "Discriminator2D", "ModifiedHiFiGANVocoder", "VocoderTrainer", "ConditionedHiFiGAN", "HiFiGANTrainer",
     "ChunkedVocoder", "MelFrontEnd", "ClipSampler", "PlainHiFiGANGenerator",
     "ECAPA_TDNN", "SE_Res2Block", "SE_Module", "Emotion2Vec", "EmbeddingExtractor",
+    "DeviceClipSampler", "resample_table",
 ]

@@ -722,3 +722,29 @@ def stft_loss(fake, real, resolutions=STFT_DEFAULT_RESOLUTIONS, floor=1e-7, weig
     N.call("mv_stft_loss", _p(fake), _p(real), B, T, len(res), ints(*(n for n, _ in res)), ints(*(h for _, h in res)), float(floor),
            float(weight), _p(sums), _p(loss), _p(gwave), int(backward), dt, _stream())
     return loss, sums, gwave
+
+
+def clip_gather(arena, descs, table, Z, P, T, key, dtype=torch.float32):
+    """Training clips out of a device-resident corpus in one launch (mv_clip_gather; the arithmetic is in the header).  arena: 1-D
+    fp32 or int16 (16-bit PCM), every utterance back to back; descs: the B 48-byte records in device memory (int64 [B, 6] or uint8
+    [B, 48]; data.CLIP_DESC); table: fp32 [Z*P + 1] (data.resample_table).  Returns wave [B, 1, T] of `dtype`."""
+    # the kernel indexes the table by Z and P and the records by B: a mismatch would be an out-of-bounds device read
+    if arena.dim() != 1 or arena.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"clip_gather: arena must be 1-D float32 or int16, got {tuple(arena.shape)} {arena.dtype}")
+    if descs.dtype not in (torch.int64, torch.uint8) or descs.numel() == 0 or (descs.numel() * descs.element_size()) % 48:
+        raise ValueError(f"clip_gather: descs must hold B >= 1 records of 48 bytes as int64 or uint8, got {tuple(descs.shape)} {descs.dtype}")
+    if not (1 <= Z <= 64 and 1 <= P <= 1024):
+        raise ValueError(f"clip_gather: Z must lie in [1, 64] and P in [1, 1024], got {Z}, {P}")
+    if table.dtype != torch.float32 or table.numel() != Z * P + 1:
+        raise ValueError(f"clip_gather: table must be float32 with Z*P + 1 = {Z * P + 1} entries, got {table.numel()} {table.dtype}")
+    if not 1 <= T <= 1 << 20:
+        raise ValueError(f"clip_gather: T must lie in [1, 2^20], got {T}")
+    if dtype not in _DT:
+        raise TypeError(f"unsupported dtype {dtype}; use float32, bfloat16 or float16")
+    _need_gpu(arena, descs, table)
+    arena, descs, table = _c(arena), _c(descs), _c(table)
+    B = descs.numel() * descs.element_size() // 48
+    wave = torch.empty(B, 1, T, device=arena.device, dtype=dtype)
+    N.call("mv_clip_gather", _p(arena), 0 if arena.dtype == torch.float32 else 1, _p(descs), _p(table), int(Z), int(P), _p(wave), B, int(T),
+           int(key), _DT[dtype], _stream())
+    return wave

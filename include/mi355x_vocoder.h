@@ -478,6 +478,28 @@ int mv_dropout_mask(uint8_t* mask, long n, float p, long seed, void* stream);
 int mv_dropout_mask_ctr(uint8_t* mask, long n, float p, long key, long ctr, void* stream);
 int mv_dropout_mask_dev(uint8_t* mask, long n, float p, const long* state_dev, long slot, void* stream);
 
+/* Training clips cut out of a device-resident corpus, with speed, gain and noise augmentation, in one launch (data.DeviceClipSampler;
+ * configs/train_config.yaml:81-85 asks for pitch_shift, time_stretch and noise_level).  arena: every utterance back to back, fp32
+ * (src_kind 0) or 16-bit PCM as int16 (src_kind 1, a sample decodes as q * 2^-15).  descs_dev: device array of B records of 48 bytes,
+ * 8-byte aligned: {int64 src_off; int64 src_len; int64 pos_q32; int64 rate_q32; float gain; float noise_std; int64 noise_ctr}.
+ *   src_off, src_len: the clip's utterance in the arena, in samples; x[j] is its decoded sample j for 0 <= j < src_len, 0 elsewhere.
+ *   pos_q32: position of output sample 0 relative to the utterance start, signed Q32.32;  rate_q32: source samples per output
+ *     sample, Q32.32, clamped in the kernel to [2^31, 2^33] (rate 0.5 .. 2).  q = pos_q32 + t * rate_q32 (exact int64),
+ *     i = q >> 32, fr = (q & 0xffffffff) * 2^-32.
+ *   copy path (rate_q32 == 2^32 and the low 32 bits of pos_q32 zero): s = x[i], no filter, bit exact.
+ *   otherwise c = min(1, 2^32 / rate_q32), s = c * sum_j x[j] h(|j - (i + fr)| c) over the j with |j - (i + fr)| c <= Z, the distance
+ *     formed as float(j - i) - fr, h linearly interpolated in `table` at u = |j - (i + fr)| c P.  table: fp32 [Z*P + 1], one wing
+ *     of the low-pass prototype sampled at k/P, k = 0..Z*P (data.resample_table).
+ *   y = gain * s + noise_std * z.  noise_std == 0: no random number is drawn, y = gain * s exactly.  Otherwise Philox4x32-10 with
+ *     counter (t/4 lo, t/4 hi, noise_ctr lo, noise_ctr hi) under key (key lo, key hi); words (r0, r1) give elements 4k and 4k+1,
+ *     (r2, r3) elements 4k+2 and 4k+3: u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24, R = sqrtf(-2 logf(u1)),
+ *     z = R cospif(2 u2), R sinpif(2 u2).
+ * wave: [B][1][T] of `dtype`, rounded once at the store.  One launch; all arithmetic fp32, positions int64.  B >= 1,
+ * 1 <= T <= 2^20, 1 <= Z <= 64, 1 <= P <= 1024, non-null pointers, src_kind 0 or 1: otherwise MV_ERR_ARG before any launch
+ * (MV_ERR_DTYPE for an unknown dtype).  The records are device data and are not validated. */
+int mv_clip_gather(const void* arena, int src_kind, const void* descs_dev, const float* table, int Z, int P,
+                   void* wave, int B, int T, long key, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Channels-last MFMA discriminator convolutions.   replaces discriminators.py:57-65 (Conv2d 3x3 pad 1) and :98-106
  * (Conv1d k15 pad 7), with their LeakyReLU(0.1), forward AND backward.   x [B][H][W][Cin], y [B][H][W][Cout], stride 1,

@@ -296,7 +296,9 @@ extern "C" int mv_conv1d_fwd(const void* x, const void* w, const void* bias, con
   MV_CHECK_ARG(x && w && y && B > 0 && Cin > 0 && Cout > 0 && Tin > 0 && ks > 0 && stride > 0 && dil > 0 && pad >= 0);
   MV_CHECK_ARG(groups > 0 && Cin % groups == 0 && Cout % groups == 0);
   MV_CHECK_ARG(nbanks >= 1 && nbanks <= MAX_BANKS && (nbanks == 1 || alpha != nullptr));
+  MV_CHECK_ARG(Tin + 2 * pad - dil * (ks - 1) - 1 >= 0);      // the kernel fits the padded input (a negative numerator truncates to Tout = 1)
   MV_CHECK_ARG(Tout == (Tin + 2 * pad - dil * (ks - 1) - 1) / stride + 1 && Tout > 0);
+  MV_CHECK_ARG(B <= 65535 && (long)groups * cdiv(Cout / groups, CO_T) <= 65535);      // grid.z, grid.y
   ConvP p{B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, groups, nbanks, act, slope, x_bs, x_cs, y_bs, y_cs, 0};
   p.xw = (TT - 1) * stride + (ks - 1) * dil + 1;
   const size_t lds = sizeof(float) * ((size_t)CI_T * p.xw + (size_t)CI_T * ks * CO_T);
@@ -319,6 +321,7 @@ extern "C" int mv_conv_transpose1d_fwd(const void* x, const void* w, const void*
   MV_CHECK_ARG(nbanks >= 1 && nbanks <= MAX_BANKS && (nbanks == 1 || alpha != nullptr));
   const int full = (Tin - 1) * stride - 2 * pad + dil * (ks - 1) + 1;
   MV_CHECK_ARG(Tout >= full && Tout < full + stride && Tout > 0);  // output_padding < stride
+  MV_CHECK_ARG(B <= 65535);                                        // grid.z
   ConvP p{B, Cin, Tin, Cout, Tout, ks, stride, pad, dil, 1, nbanks, act, slope,
           (long)Cin * Tin, (long)Tin, (long)Cout * Tout, (long)Tout, 0};
   p.xw = (TT - 1 + (ks - 1) * dil) / stride + 2;

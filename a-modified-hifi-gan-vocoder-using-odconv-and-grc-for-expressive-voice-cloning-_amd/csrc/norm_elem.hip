@@ -327,8 +327,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
   const uint8_t* mr = mask ? mask + (long)bc * Tn : nullptr;
   T* yr = y + (long)b * y_bs + (long)c * y_cs;
   // 16-bit rows that allow it move 16 bytes per thread and access; the activation is chosen once (functor), not per element
+  // (the mask is read as one 8-byte word per 8 elements: its rows start at mask + bc * Tn, whole words when Tn % 8 == 0)
   const bool vec = sizeof(T) == 2 && all_mult8(Tn, x_bs, x_cs, r_bs, r_cs, y_bs, y_cs) &&
-                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0;
+                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0 && ((uintptr_t)mask & 7) == 0;
   auto body = [&](auto actf) {
     if (vec) {
       for (int t = (blockIdx.x * blockDim.x + threadIdx.x) * 8; t < Tn; t += gridDim.x * blockDim.x * 8) {
@@ -638,7 +639,7 @@ extern "C" int mv_groupnorm_apply(const void* x, const float* mean, const float*
   MV_CHECK_ARG(x && mean && rstd && y && B > 0 && C > 0 && T_ > 0 && G > 0 && C % G == 0 && (long)B * C <= 65535);
   // 16-bit rows that qualify for the 16-byte path (same test as in the kernel) need 8x fewer threads along T
   const bool vec = dtype != MV_F32 && all_mult8(T_, x_bs, x_cs, r_bs, r_cs, y_bs, y_cs) &&
-                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0;
+                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0 && ((uintptr_t)mask & 7) == 0;
   dim3 grid(grid_for(vec ? cdiv(T_, 8) : T_, 256, 64), B * C);
   MV_DISPATCH(dtype, hipLaunchKernelGGL(gn_apply_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, mean,
                                         rstd, (const T*)gw, (const T*)gb, (const T*)res, mask, mask_scale, (T*)y, C,

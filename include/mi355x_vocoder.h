@@ -61,7 +61,9 @@ int mv_odconv_attn_fwd(const void* x, const void* w, const void* bias, float* al
  *   y[b,o,t] = act( sum_k alpha[b,k] ( sum_{c,j} w[k,o,c,j] x[b,c,t*stride-pad+j*dil] + bias[k,o] ) ) + res[b,o,t]
  *   w [nbanks, Cout, Cin/groups, ks]; bias [nbanks, Cout] or NULL; res (optional) has y's layout.
  *   x_bs/y_bs: batch strides in elements, x_cs/y_cs: channel strides (time stride is 1) - lets a call read or
- *   write a channel slice of a wider buffer (the torch.cat of grc_lora.py:159 is written in place). */
+ *   write a channel slice of a wider buffer (the torch.cat of grc_lora.py:159 is written in place).
+ *   Tout = (Tin + 2*pad - dil*(ks-1) - 1) / stride + 1 with a non-negative numerator; B <= 65535 and
+ *   groups * ceil(Cout/groups / 32) <= 65535 (grid.z, grid.y); more than 160 KB of LDS (ks ~ 159 at stride 1): MV_ERR_UNSUPPORTED. */
 int mv_conv1d_fwd(const void* x, const void* w, const void* bias, const float* alpha, const void* res, void* y,
                   int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil, int groups,
                   int nbanks, int act, float slope,
@@ -69,7 +71,7 @@ int mv_conv1d_fwd(const void* x, const void* w, const void* bias, const float* a
 
 /* (Dynamic) transposed 1-D convolution.   replaces odconv.py:187-204 (+ the nn.LeakyReLU(0.1) of SURVEY §A item 2 when act=LRELU)
  *   y[b,o,u] = act( sum_k alpha[b,k] ( sum_{c,j: u = t*stride - pad + j*dil} w[k,c,o,j] x[b,c,t] + bias[k,o] ) )
- *   w [nbanks, Cin, Cout, ks]; Tout = (Tin-1)*stride - 2*pad + dil*(ks-1) + out_pad + 1; groups must be 1. */
+ *   w [nbanks, Cin, Cout, ks]; Tout = (Tin-1)*stride - 2*pad + dil*(ks-1) + out_pad + 1, out_pad < stride; groups must be 1; B <= 65535. */
 int mv_conv_transpose1d_fwd(const void* x, const void* w, const void* bias, const float* alpha, void* y,
                             int B, int Cin, int Tin, int Cout, int Tout, int ks, int stride, int pad, int dil,
                             int nbanks, int act, float slope, int dtype, void* stream);
@@ -83,8 +85,9 @@ int mv_conv2d_fwd(const void* x, const void* w, const void* bias, void* y,
 /* ------------------------------------------------------------------------------------------------
  * GroupNorm, two-phase.   replaces grc_lora.py:58,161 and generator.py:170 (nn.GroupNorm, eps 1e-5)
  *   stats: mean/rstd fp32 [B,G] over (C/G channels x T) of x (biased variance).
- *   apply: y = act( (x-mean)*rstd*gw[c] + gb[c] ) * (mask ? mask[b,c,t]*mask_scale : 1) + res
- *   strides as in mv_conv1d_fwd (x and res may be channel slices). mask: uint8 keep-mask of nn.Dropout (grc_lora.py:162). */
+ *   apply: y = act( (x-mean)*rstd*gw[c] + gb[c] ) * (mask ? (mask[b,c,t] ? mask_scale : 0) : 1) + res
+ *   strides as in mv_conv1d_fwd (x and res may be channel slices). mask: dense uint8 keep-mask of nn.Dropout (grc_lora.py:162), any
+ *   non-zero byte keeps; any address (16-bit rows take the 16-byte path only when it is 8-byte aligned).  B * C <= 65535. */
 int mv_groupnorm_stats(const void* x, float* mean, float* rstd, int B, int C, int T, int G, float eps,
                        long x_bs, long x_cs, int dtype, void* stream);
 int mv_groupnorm_apply(const void* x, const float* mean, const float* rstd, const void* gw, const void* gb,
